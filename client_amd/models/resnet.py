@@ -125,6 +125,45 @@ class BiasAct(nn.Module):
         return out.relu_() if self.relu_flag else out
 
 
+class BiasReluMaxPool(nn.Module):
+    """ResNet stem epilogue: per-channel bias + ReLU + 3x3 stride-2
+    pad-1 max-pool as ONE CDNA4 kernel pass over the biasless conv
+    output. Separately this is a bias+ReLU pass that reads and writes
+    the 64x112x112 map and torch's NCHW max-pool reading it again; the
+    fused kernel reads it once and writes only the pooled map, with
+    every element computed as BiasAct does (fp32 add, ReLU, RNE to
+    bf16), so the result is bit-identical.
+
+    Falls back to the torch sequence on CPU, for non-bf16 or
+    non-contiguous input, and when CLIENT_AMD_FUSED_BIAS=0."""
+
+    def __init__(self, bias):
+        super().__init__()
+        self.register_buffer("bias", bias.detach().float())
+
+    def forward(self, x):
+        import torch
+        import torch.nn.functional as F
+
+        if (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
+                and x.is_contiguous()
+                and os.environ.get("CLIENT_AMD_FUSED_BIAS", "1") != "0"):
+            from ..ops import hip_runtime as hr
+
+            if self.bias.dtype != torch.float32:
+                # TorchModel's .to(bf16) sweeps buffers; kernel reads fp32
+                self.bias.data = self.bias.data.float()
+            n, c, h, w = x.shape
+            out = torch.empty((n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1),
+                              device=x.device, dtype=x.dtype)
+            hr.bias_relu_maxpool_bf16(
+                x.data_ptr(), self.bias.data_ptr(), out.data_ptr(), n * c,
+                c, h, w, torch.cuda.current_stream().cuda_stream)
+            return out
+        out = x + self.bias.view(1, -1, *([1] * (x.dim() - 2))).to(x.dtype)
+        return F.max_pool2d(out.relu_(), 3, 2, 1)
+
+
 class BiasResAct(nn.Module):
     """Bottleneck-exit fusion: out = relu(x + bias[c] + residual) in ONE
     CDNA4 kernel pass. After BN folding torch-on-ROCm runs this as three
@@ -206,6 +245,19 @@ def _strip_bias(conv):
     return bias
 
 
+def _is_stem_pool(pool):
+    """True for the 3x3 stride-2 pad-1 max-pool BiasReluMaxPool fuses."""
+    def pair(v):
+        return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+    return (isinstance(pool, nn.MaxPool2d)
+            and pair(pool.kernel_size) == (3, 3)
+            and pair(pool.stride) == (2, 2)
+            and pair(pool.padding) == (1, 1)
+            and pair(pool.dilation) == (1, 1)
+            and not pool.ceil_mode and not pool.return_indices)
+
+
 def fold_batchnorm(module, fuse_eltwise=None):
     """Fold every Conv2d -> BatchNorm2d pair into the conv weights
     (algebraically exact in eval mode: W' = W*g/sqrt(v+eps),
@@ -214,8 +266,10 @@ def fold_batchnorm(module, fuse_eltwise=None):
     (profiles/serving_rocprof_r01.txt); folding removes them entirely.
 
     fuse_eltwise=True additionally rewrites every Bottleneck as a
-    FusedBottleneck and the stem bias+relu as one BiasAct pass, so the
-    folded conv biases never run as separate torch elementwise kernels
+    FusedBottleneck and the stem bias+relu+maxpool as one
+    BiasReluMaxPool pass (standing in the bn1 slot; relu and maxpool
+    become Identity), so the folded conv biases never run as separate
+    torch elementwise kernels
     (default; CLIENT_AMD_FUSED_BIAS=0 disables). Pairs are detected by
     _modules adjacency (conv immediately followed by its BN, matching
     this file and torchvision layouts)."""
@@ -247,13 +301,20 @@ def fold_batchnorm(module, fuse_eltwise=None):
                 m._modules[name] = FusedBottleneck(
                     c1, ba1, c2, ba2, c3, ds_conv, exit_bias
                 )
-        # stem: conv1+bn1+relu -> biasless conv + one BiasAct(relu) pass
+        # stem: conv1+bn1+relu+maxpool -> biasless conv + one
+        # BiasReluMaxPool pass in the bn1 slot (one BiasAct(relu) pass
+        # and the model's own pool when the pool is not 3x3/s2/p1)
         if (isinstance(getattr(module, "conv1", None), nn.Conv2d)
                 and isinstance(getattr(module, "bn1", None),
                                nn.BatchNorm2d)):
             fused = fuse_pair(module.conv1, module.bn1)
             module.conv1 = fused
-            module.bn1 = BiasAct(_strip_bias(fused), relu=True)
+            if (isinstance(getattr(module, "relu", None), nn.ReLU)
+                    and _is_stem_pool(getattr(module, "maxpool", None))):
+                module.bn1 = BiasReluMaxPool(_strip_bias(fused))
+                module.maxpool = nn.Identity()
+            else:
+                module.bn1 = BiasAct(_strip_bias(fused), relu=True)
             module.relu = nn.Identity()
 
     # generic pass folds any remaining conv->bn adjacency (stem when

@@ -360,6 +360,15 @@ static void bias_res_act_bf16(uintptr_t x, uintptr_t res, uintptr_t bias,
       reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
+static void bias_relu_maxpool_bf16(uintptr_t x, uintptr_t bias, uintptr_t out,
+                                   long n_planes, int channels, int h, int w,
+                                   uintptr_t stream_handle) {
+  HIP_CHECK(ca_bias_relu_maxpool_bf16(
+      reinterpret_cast<const void*>(x), reinterpret_cast<const void*>(bias),
+      reinterpret_cast<void*>(out), n_planes, channels, h, w,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
 static void rmsnorm_bf16(uintptr_t x, uintptr_t w, uintptr_t out,
                          long rows, int dim, double eps,
                          uintptr_t stream_handle) {
@@ -487,6 +496,10 @@ PYBIND11_MODULE(_hip_c, m) {
   m.def("bias_res_act_cl_bf16", &bias_res_act_cl_bf16, py::arg("x"),
         py::arg("res"), py::arg("bias"), py::arg("out"), py::arg("n"),
         py::arg("channels"), py::arg("relu"), py::arg("stream_handle"));
+  m.def("bias_relu_maxpool_bf16", &bias_relu_maxpool_bf16, py::arg("x"),
+        py::arg("bias"), py::arg("out"), py::arg("n_planes"),
+        py::arg("channels"), py::arg("h"), py::arg("w"),
+        py::arg("stream_handle"));
   m.def("rmsnorm_bf16", &rmsnorm_bf16, py::arg("x"), py::arg("w"),
         py::arg("out"), py::arg("rows"), py::arg("dim"), py::arg("eps"),
         py::arg("stream_handle"));
