@@ -115,6 +115,14 @@ extern "C" __global__ void cast_bf16_fp32_v2_kernel(
 
 // fp32 -> fp8 e4m3 (OCP fn, the CDNA4-native format — NOT MI300X fnuz;
 // cdna_hip_programming.md §4). RNE via the __hip_fp8_e4m3 HW convert.
+// Contract (tests/kernel_refs.py:fp8_e4m3_encode is the executable form):
+//   - round to nearest, ties to the even code; subnormal step 2^-9;
+//   - __hip_fp8_e4m3 converts with __HIP_SATFINITE: finite inputs whose
+//     magnitude rounds above 448 SATURATE to +-448 (0x7E / 0xFE). This
+//     differs from torch.float8_e4m3fn, which yields NaN above 464;
+//   - NaN and +-Inf pass through the clamp and give a NaN code
+//     ((code & 0x7F) == 0x7F);
+//   - the sign of a zero result is preserved.
 extern "C" __global__ void cast_fp32_fp8e4m3_kernel(const float* __restrict__ src,
                                                     uint8_t* __restrict__ dst,
                                                     long n) {
@@ -484,8 +492,12 @@ __global__ void transpose_tiled_kernel(const T* __restrict__ src,
 // generic u16 path measured 2.3 TB/s vs 4.2 for fp32). Layout per
 // 64x64 tile: load phase writes u32 pairs along the source-contiguous
 // dim; store phase reads two adjacent tile rows and packs a u32 along
-// the destination-contiguous dim. Only used for fully-covered tiles;
-// ragged edges fall back to the scalar path in the launcher.
+// the destination-contiguous dim. Ragged tile edges (odd rows/cols,
+// partial tiles) are handled in the kernel by the single-element
+// branches. The u32 global accesses need 4-byte alignment: r, c and the
+// tile origins are even, so the launcher selects this kernel only when
+// src and dst are 4-byte aligned and col_stride, s0, s1 and cols are
+// even; everything else goes to transpose_tiled_kernel<uint16_t>.
 extern "C" __global__ void transpose_tiled_pair16_kernel(
     const uint16_t* __restrict__ src, uint16_t* __restrict__ dst, long rows,
     long cols, long col_stride, long s0, long s1, long d1) {
@@ -791,8 +803,16 @@ extern "C" hipError_t ca_gather_pack(const void* src, void* dst,
                                                   stream);
       case 2: {
         // pair-per-lane variant restores full bus width for 2-byte
-        // elements (u16 path: 2.3 TB/s; fp32: 4.2)
+        // elements (u16 path: 2.3 TB/s; fp32: 4.2). Its u32 accesses
+        // are aligned only for 4-byte-aligned bases and even element
+        // offsets; any odd stride/extent/base takes the u16 kernel.
         const long rows = shape[2], cols = shape[3];
+        const bool pair_aligned =
+            (((uintptr_t)src | (uintptr_t)dst) & 3) == 0 &&
+            ((strides[3] | strides[0] | strides[1] | cols) & 1) == 0;
+        if (!pair_aligned)
+          return ca_transpose_tiled_launch<uint16_t>(src, dst, shape,
+                                                     strides, stream);
         dim3 grid((uint32_t)((rows + CA_TILE - 1) / CA_TILE),
                   (uint32_t)((cols + CA_TILE - 1) / CA_TILE),
                   (uint32_t)(shape[0] * shape[1]));
@@ -1447,6 +1467,7 @@ extern "C" hipError_t ca_rmsnorm_bf16(const void* x, const void* w, void* out,
                                       long rows, int dim, float eps,
                                       hipStream_t stream) {
   if (dim % 8 != 0) return hipErrorInvalidValue;
+  if (rows == 0) return hipSuccess;  // nothing to do; a zero grid is invalid
   hipLaunchKernelGGL(rmsnorm_bf16_kernel, dim3((uint32_t)rows), dim3(256), 0,
                      stream, (const uint16_t*)x, (const uint16_t*)w,
                      (uint16_t*)out, dim, eps);

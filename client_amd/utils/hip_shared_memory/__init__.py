@@ -135,13 +135,45 @@ def set_shared_memory_region(shm_handle, input_values, offset=0):
         cur += nbytes
 
 
+_CAST_WIRE_ITEMSIZE = {"BF16": 2, "FP8E4M3": 1, "FP32": 4}
+
+
+def _check_cast_range(shm_handle, wire_datatype, n, offset):
+    """The cast kernels write/read n wire elements at base + offset; the
+    whole range must lie inside the region (nothing is launched
+    otherwise)."""
+    itemsize = _CAST_WIRE_ITEMSIZE.get(wire_datatype)
+    if itemsize is None:
+        raise CudaSharedMemoryException(
+            f"unsupported cast datatype {wire_datatype}"
+        )
+    if offset < 0:
+        raise CudaSharedMemoryException("offset must be non-negative")
+    if offset + n * itemsize > shm_handle._byte_size:
+        raise CudaSharedMemoryException(
+            "cast range exceeds shared memory region size"
+        )
+
+
 def set_shared_memory_region_cast(shm_handle, input_value, wire_datatype,
                                   offset=0, sync=True):
     """MI355X pack path: upload fp32 host data to device scratch once,
     then run the CDNA4 cast kernel into the region (bf16 wire-exact
-    truncation / fp8 e4m3 RNE). Returns the packed byte size."""
+    truncation / fp8 e4m3 RNE). Returns the packed byte size.
+
+    FP8E4M3 contract (OCP e4m3fn codes): round to nearest, ties to the
+    even code (subnormal step 2**-9); finite values that round above 448
+    saturate to +-448 (codes 0x7E / 0xFE) — unlike
+    ``torch.float8_e4m3fn``, which turns everything above 464 into NaN;
+    NaN and +-Inf give a NaN code (``code & 0x7F == 0x7F``); the sign of
+    a zero result is preserved.
+
+    Raises CudaSharedMemoryException, before anything is uploaded or
+    launched, if ``[offset, offset + packed size)`` does not lie inside
+    the region."""
     arr = np.ascontiguousarray(input_value, dtype=np.float32)
     n = arr.size
+    _check_cast_range(shm_handle, wire_datatype, n, offset)
     scratch = shm_handle._ensure_scratch(arr.nbytes)
     hr.memcpy_h2d(scratch, arr.reshape(-1).view(np.uint8), arr.nbytes,
                   shm_handle._device_id, False)
@@ -162,8 +194,10 @@ def set_shared_memory_region_cast(shm_handle, input_value, wire_datatype,
 
 def get_contents_cast(shm_handle, wire_datatype, shape, offset=0):
     """Inverse of set_shared_memory_region_cast: device unpack kernel
-    (bf16/fp8 -> fp32) then one D2H copy; returns fp32 numpy."""
+    (bf16/fp8 -> fp32) then one D2H copy; returns fp32 numpy. Raises
+    CudaSharedMemoryException if the source range leaves the region."""
     n = int(np.prod(shape))
+    _check_cast_range(shm_handle, wire_datatype, n, offset)
     scratch = shm_handle._ensure_scratch(n * 4)
     src = shm_handle._base_addr + offset
     if wire_datatype == "BF16":
