@@ -4,17 +4,27 @@
 // memory (hipMalloc + hipIpcGetMemHandle / hipIpcOpenMemHandle), async
 // copies on cached per-device streams, and hand-written gfx950 kernels
 // for the work the reference does on the CPU (per-element BF16 loops,
-// OpenCV preprocess):
+// OpenCV preprocess) and for the served models' hot paths. Bound here:
+//   - device_count / mem_info / malloc / free, ipc_{get,open,close}_mem_handle
+//   - memcpy_h2d / memcpy_d2h / memcpy_d2h_into / memcpy_d2d /
+//     memcpy_peer_async, stream_sync / stream_handle / stream_fence,
+//     device_enable_peer_access / device_sync
 //   - cast_fp32_bf16 / cast_bf16_fp32   (wire-exact truncate / zero-pad)
 //   - cast_fp32_fp8e4m3 / cast_fp8e4m3_fp32 (OCP e4m3fn, CDNA4 native)
 //   - gather_pack (strided -> contiguous, lifts the reference's DLPack
 //     contiguity restriction, cuda_shared_memory/__init__.py:328-388)
-//   - image_preprocess (u8 HWC -> resize bilinear -> normalize -> CHW,
-//     replaces image_client.cc:86-190's OpenCV path)
+//   - image_preprocess / image_preprocess_batched (u8 HWC -> resize
+//     bilinear -> normalize -> CHW, replaces image_client.cc:86-190's
+//     OpenCV path)
+//   - bias_act_bf16 / bias_res_act_bf16 / bias_res_act_cl_bf16 /
+//     bias_relu_maxpool_bf16 (ResNet50 conv epilogues, NCHW and NHWC)
+//   - rmsnorm_bf16 / rope_decode_bf16 / rope_scatter_decode_bf16 /
+//     decode_gemm_bf16 (LLM decode step)
 //
-// All kernels are memory-bound streaming kernels: 16 B/lane vectorized
-// access, 256-thread blocks (4 waves of 64), grid-stride with the grid
-// capped at 2048 workgroups (cdna_hip_programming.md §6 G11/G13).
+// The cast, pack and preprocess kernels are memory-bound streaming
+// kernels: 16 B/lane vectorized access, 256-thread blocks (4 waves of
+// 64), grid-stride with the grid capped at 2048 workgroups
+// (cdna_hip_programming.md §6 G11/G13).
 // Pure HIP — no CUDA headers, no torch dependency; torch interop is via
 // DLPack in Python.
 
@@ -54,14 +64,11 @@ namespace py = pybind11;
 // Launch helpers
 // ---------------------------------------------------------------------------
 
-static inline int grid_for(long work_items) {
-  // memory-bound streaming grid: cap at 2048 workgroups, grid-stride the
-  // rest (G11). 256 CUs x 8 blocks/CU.
-  long blocks = (work_items + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
+// raw device pointers cross the Python boundary as integers
+static inline const void* cptr(uintptr_t p) {
+  return reinterpret_cast<const void*>(p);
 }
+static inline void* mptr(uintptr_t p) { return reinterpret_cast<void*>(p); }
 
 // Per-device cached streams: [0] = copy/pack stream, [1] = side stream for
 // collective overlap (SURVEY.md §2.9 row 5 mandates the second stream).
@@ -81,6 +88,14 @@ static hipStream_t get_stream(int device, int idx = 0) {
     HIP_CHECK(hipSetDevice(prev));
   }
   return vec[idx];
+}
+
+// blocks until the stream drains (GIL released) when the caller asked
+// for a synchronous call
+static void sync_if(bool sync, hipStream_t s) {
+  if (!sync) return;
+  py::gil_scoped_release release;
+  HIP_CHECK(hipStreamSynchronize(s));
 }
 
 // ---------------------------------------------------------------------------
@@ -115,12 +130,12 @@ static uintptr_t hip_malloc(int device, size_t byte_size) {
 }
 
 static void hip_free(uintptr_t ptr) {
-  HIP_CHECK(hipFree(reinterpret_cast<void*>(ptr)));
+  HIP_CHECK(hipFree(mptr(ptr)));
 }
 
 static py::bytes ipc_get_mem_handle(uintptr_t ptr) {
   hipIpcMemHandle_t handle;
-  HIP_CHECK(hipIpcGetMemHandle(&handle, reinterpret_cast<void*>(ptr)));
+  HIP_CHECK(hipIpcGetMemHandle(&handle, mptr(ptr)));
   return py::bytes(reinterpret_cast<const char*>(&handle), sizeof(handle));
 }
 
@@ -137,7 +152,7 @@ static uintptr_t ipc_open_mem_handle(py::bytes raw) {
 }
 
 static void ipc_close_mem_handle(uintptr_t ptr) {
-  HIP_CHECK(hipIpcCloseMemHandle(reinterpret_cast<void*>(ptr)));
+  HIP_CHECK(hipIpcCloseMemHandle(mptr(ptr)));
 }
 
 static void memcpy_h2d(uintptr_t dst, py::buffer src, size_t byte_size,
@@ -148,7 +163,7 @@ static void memcpy_h2d(uintptr_t dst, py::buffer src, size_t byte_size,
   hipStream_t s = get_stream(device);
   {
     py::gil_scoped_release release;
-    HIP_CHECK(hipMemcpyAsync(reinterpret_cast<void*>(dst), info.ptr, byte_size,
+    HIP_CHECK(hipMemcpyAsync(mptr(dst), info.ptr, byte_size,
                              hipMemcpyHostToDevice, s));
     if (sync) HIP_CHECK(hipStreamSynchronize(s));
   }
@@ -159,7 +174,7 @@ static py::bytes memcpy_d2h(uintptr_t src, size_t byte_size, int device) {
   hipStream_t s = get_stream(device);
   {
     py::gil_scoped_release release;
-    HIP_CHECK(hipMemcpyAsync(&out[0], reinterpret_cast<void*>(src), byte_size,
+    HIP_CHECK(hipMemcpyAsync(&out[0], mptr(src), byte_size,
                              hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
   }
@@ -174,7 +189,7 @@ static void memcpy_d2h_into(uintptr_t src, py::buffer dst, size_t byte_size,
   hipStream_t s = get_stream(device);
   {
     py::gil_scoped_release release;
-    HIP_CHECK(hipMemcpyAsync(info.ptr, reinterpret_cast<void*>(src), byte_size,
+    HIP_CHECK(hipMemcpyAsync(info.ptr, mptr(src), byte_size,
                              hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
   }
@@ -185,8 +200,7 @@ static void memcpy_d2d(uintptr_t dst, uintptr_t src, size_t byte_size,
   hipStream_t s = get_stream(device);
   {
     py::gil_scoped_release release;
-    HIP_CHECK(hipMemcpyAsync(reinterpret_cast<void*>(dst),
-                             reinterpret_cast<void*>(src), byte_size,
+    HIP_CHECK(hipMemcpyAsync(mptr(dst), mptr(src), byte_size,
                              hipMemcpyDeviceToDevice, s));
     if (sync) HIP_CHECK(hipStreamSynchronize(s));
   }
@@ -214,8 +228,7 @@ static void memcpy_peer_async(uintptr_t dst, int dst_device, uintptr_t src,
   // bound; direct scatter is not)
   hipStream_t s = get_stream(src_device, stream_idx);
   py::gil_scoped_release release;
-  HIP_CHECK(hipMemcpyPeerAsync(reinterpret_cast<void*>(dst), dst_device,
-                               reinterpret_cast<void*>(src), src_device,
+  HIP_CHECK(hipMemcpyPeerAsync(mptr(dst), dst_device, mptr(src), src_device,
                                byte_size, s));
 }
 
@@ -257,49 +270,29 @@ static void device_sync() {
 static void cast_fp32_bf16(uintptr_t src, uintptr_t dst, long n, int device,
                            bool sync, int stream_idx) {
   hipStream_t s = get_stream(device, stream_idx);
-  HIP_CHECK(ca_cast_fp32_bf16(reinterpret_cast<const void*>(src),
-                 reinterpret_cast<void*>(dst), n, s));
-  
-  if (sync) {
-    py::gil_scoped_release release;
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
+  HIP_CHECK(ca_cast_fp32_bf16(cptr(src), mptr(dst), n, s));
+  sync_if(sync, s);
 }
 
 static void cast_bf16_fp32(uintptr_t src, uintptr_t dst, long n, int device,
                            bool sync, int stream_idx) {
   hipStream_t s = get_stream(device, stream_idx);
-  HIP_CHECK(ca_cast_bf16_fp32(reinterpret_cast<const void*>(src),
-                 reinterpret_cast<void*>(dst), n, s));
-  
-  if (sync) {
-    py::gil_scoped_release release;
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
+  HIP_CHECK(ca_cast_bf16_fp32(cptr(src), mptr(dst), n, s));
+  sync_if(sync, s);
 }
 
 static void cast_fp32_fp8e4m3(uintptr_t src, uintptr_t dst, long n, int device,
                               bool sync, int stream_idx) {
   hipStream_t s = get_stream(device, stream_idx);
-  HIP_CHECK(ca_cast_fp32_fp8e4m3(reinterpret_cast<const void*>(src),
-                 reinterpret_cast<void*>(dst), n, s));
-  
-  if (sync) {
-    py::gil_scoped_release release;
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
+  HIP_CHECK(ca_cast_fp32_fp8e4m3(cptr(src), mptr(dst), n, s));
+  sync_if(sync, s);
 }
 
 static void cast_fp8e4m3_fp32(uintptr_t src, uintptr_t dst, long n, int device,
                               bool sync, int stream_idx) {
   hipStream_t s = get_stream(device, stream_idx);
-  HIP_CHECK(ca_cast_fp8e4m3_fp32(reinterpret_cast<const void*>(src),
-                 reinterpret_cast<void*>(dst), n, s));
-  
-  if (sync) {
-    py::gil_scoped_release release;
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
+  HIP_CHECK(ca_cast_fp8e4m3_fp32(cptr(src), mptr(dst), n, s));
+  sync_if(sync, s);
 }
 
 static void gather_pack(uintptr_t src, uintptr_t dst, int elem_size,
@@ -312,21 +305,18 @@ static void gather_pack(uintptr_t src, uintptr_t dst, int elem_size,
   }
   if (shape.size() > 4) throw std::runtime_error("gather_pack: >4D unsupported");
   hipStream_t s = get_stream(device);
-  HIP_CHECK(ca_gather_pack(reinterpret_cast<const void*>(src),
-                           reinterpret_cast<void*>(dst), elem_size,
-                           shape.data(), strides.data(), s));
-  if (sync) {
-    py::gil_scoped_release release;
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
+  HIP_CHECK(ca_gather_pack(cptr(src), mptr(dst), elem_size, shape.data(),
+                           strides.data(), s));
+  sync_if(sync, s);
 }
+
+// The model-side kernels launch on the CALLER's stream (torch's current
+// stream) so they compose with torch ops and hipGraph capture.
 
 static void bias_act_bf16(uintptr_t x, uintptr_t bias, uintptr_t out,
                           long n_planes, long plane, int channels,
                           bool relu, uintptr_t stream_handle) {
-  HIP_CHECK(ca_bias_act_bf16(reinterpret_cast<const void*>(x),
-                             reinterpret_cast<const void*>(bias),
-                             reinterpret_cast<void*>(out), n_planes, plane,
+  HIP_CHECK(ca_bias_act_bf16(cptr(x), cptr(bias), mptr(out), n_planes, plane,
                              channels, relu ? 1 : 0,
                              reinterpret_cast<hipStream_t>(stream_handle)));
 }
@@ -334,8 +324,7 @@ static void bias_act_bf16(uintptr_t x, uintptr_t bias, uintptr_t out,
 static void decode_gemm_bf16(uintptr_t x, uintptr_t w, uintptr_t y, int n,
                              int k, uintptr_t stream_handle) {
   HIP_CHECK(ca_decode_gemm_bf16(
-      reinterpret_cast<const void*>(x), reinterpret_cast<const void*>(w),
-      reinterpret_cast<void*>(y), n, k,
+      cptr(x), cptr(w), mptr(y), n, k,
       reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
@@ -343,9 +332,7 @@ static void bias_res_act_cl_bf16(uintptr_t x, uintptr_t res, uintptr_t bias,
                                  uintptr_t out, long n, int channels,
                                  bool relu, uintptr_t stream_handle) {
   HIP_CHECK(ca_bias_res_act_cl_bf16(
-      reinterpret_cast<const void*>(x), reinterpret_cast<const void*>(res),
-      reinterpret_cast<const void*>(bias), reinterpret_cast<void*>(out), n,
-      channels, relu ? 1 : 0,
+      cptr(x), cptr(res), cptr(bias), mptr(out), n, channels, relu ? 1 : 0,
       reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
@@ -354,43 +341,32 @@ static void bias_res_act_bf16(uintptr_t x, uintptr_t res, uintptr_t bias,
                               int channels, bool relu,
                               uintptr_t stream_handle) {
   HIP_CHECK(ca_bias_res_act_bf16(
-      reinterpret_cast<const void*>(x), reinterpret_cast<const void*>(res),
-      reinterpret_cast<const void*>(bias), reinterpret_cast<void*>(out),
-      n_planes, plane, channels, relu ? 1 : 0,
-      reinterpret_cast<hipStream_t>(stream_handle)));
+      cptr(x), cptr(res), cptr(bias), mptr(out), n_planes, plane, channels,
+      relu ? 1 : 0, reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
 static void bias_relu_maxpool_bf16(uintptr_t x, uintptr_t bias, uintptr_t out,
                                    long n_planes, int channels, int h, int w,
                                    uintptr_t stream_handle) {
   HIP_CHECK(ca_bias_relu_maxpool_bf16(
-      reinterpret_cast<const void*>(x), reinterpret_cast<const void*>(bias),
-      reinterpret_cast<void*>(out), n_planes, channels, h, w,
+      cptr(x), cptr(bias), mptr(out), n_planes, channels, h, w,
       reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
 static void rmsnorm_bf16(uintptr_t x, uintptr_t w, uintptr_t out,
                          long rows, int dim, double eps,
                          uintptr_t stream_handle) {
-  // launches on the CALLER's stream (torch's current stream) so it
-  // composes with torch ops and hipGraph capture
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream_handle);
-  HIP_CHECK(ca_rmsnorm_bf16(reinterpret_cast<const void*>(x),
-                            reinterpret_cast<const void*>(w),
-                            reinterpret_cast<void*>(out), rows, dim,
-                            (float)eps, s));
+  HIP_CHECK(ca_rmsnorm_bf16(cptr(x), cptr(w), mptr(out), rows, dim,
+                            (float)eps,
+                            reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
 static void rope_decode_bf16(uintptr_t q, uintptr_t k, uintptr_t cos_tab,
                              uintptr_t sin_tab, uintptr_t pos, int b, int hq,
                              int hk, int d, uintptr_t stream_handle) {
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream_handle);
-  HIP_CHECK(ca_rope_decode_bf16(reinterpret_cast<void*>(q),
-                                reinterpret_cast<void*>(k),
-                                reinterpret_cast<const void*>(cos_tab),
-                                reinterpret_cast<const void*>(sin_tab),
-                                reinterpret_cast<const void*>(pos), b, hq, hk,
-                                d, s));
+  HIP_CHECK(ca_rope_decode_bf16(
+      mptr(q), mptr(k), cptr(cos_tab), cptr(sin_tab), cptr(pos), b, hq, hk, d,
+      reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
 static void rope_scatter_decode_bf16(uintptr_t q, uintptr_t k, uintptr_t v,
@@ -400,11 +376,8 @@ static void rope_scatter_decode_bf16(uintptr_t q, uintptr_t k, uintptr_t v,
                                      int d, long cache_len, float q_scale,
                                      uintptr_t stream_handle) {
   HIP_CHECK(ca_rope_scatter_decode_bf16(
-      reinterpret_cast<void*>(q), reinterpret_cast<const void*>(k),
-      reinterpret_cast<const void*>(v), reinterpret_cast<void*>(ck),
-      reinterpret_cast<void*>(cv), reinterpret_cast<const void*>(cos_tab),
-      reinterpret_cast<const void*>(sin_tab),
-      reinterpret_cast<const void*>(pos), b, hq, hk, d, cache_len, q_scale,
+      mptr(q), cptr(k), cptr(v), mptr(ck), mptr(cv), cptr(cos_tab),
+      cptr(sin_tab), cptr(pos), b, hq, hk, d, cache_len, q_scale,
       reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
@@ -415,14 +388,10 @@ static void image_preprocess(uintptr_t src, uintptr_t dst, int ih, int iw,
   if (mean.size() != 3 || stdev.size() != 3)
     throw std::runtime_error("mean/std must have 3 channels");
   hipStream_t s = get_stream(device);
-  HIP_CHECK(ca_image_preprocess(reinterpret_cast<const void*>(src),
-                                reinterpret_cast<void*>(dst), ih, iw, oh, ow,
-                                mode, out_bf16 ? 1 : 0, mean.data(),
-                                stdev.data(), s));
-  if (sync) {
-    py::gil_scoped_release release;
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
+  HIP_CHECK(ca_image_preprocess(cptr(src), mptr(dst), ih, iw, oh, ow, mode,
+                                out_bf16 ? 1 : 0, mean.data(), stdev.data(),
+                                s));
+  sync_if(sync, s);
 }
 
 static void image_preprocess_batched(uintptr_t src, uintptr_t dst,
@@ -435,13 +404,9 @@ static void image_preprocess_batched(uintptr_t src, uintptr_t dst,
     throw std::runtime_error("mean/std must have 3 channels");
   hipStream_t s = get_stream(device);
   HIP_CHECK(ca_image_preprocess_batched(
-      reinterpret_cast<const void*>(src), reinterpret_cast<void*>(dst),
-      n_images, ih, iw, oh, ow, mode, out_bf16 ? 1 : 0, mean.data(),
-      stdev.data(), s));
-  if (sync) {
-    py::gil_scoped_release release;
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
+      cptr(src), mptr(dst), n_images, ih, iw, oh, ow, mode, out_bf16 ? 1 : 0,
+      mean.data(), stdev.data(), s));
+  sync_if(sync, s);
 }
 
 PYBIND11_MODULE(_hip_c, m) {

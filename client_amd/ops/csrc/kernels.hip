@@ -3,6 +3,10 @@
 // are C ABI taking an explicit hipStream_t so both stacks compose the
 // kernels with their own streams/graphs. See client_amd/ops/csrc
 // provenance comments on each kernel.
+//
+// Kernel bodies shared between entry points are templates; each
+// launched kernel is a thin extern "C" entry point around its body so
+// the symbol names in rocprofv3 traces stay stable.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -21,97 +25,74 @@ inline int ca_grid_for(long work_items) {
   return (int)blocks;
 }
 
+// ---------------------------------------------------------------------------
+// bf16 helpers. Two float -> bf16 roundings live in this file and must
+// not be mixed: truncation for the wire codec, integer round-to-
+// nearest-even for the epilogue, stem and decode-GEMM kernels.
+// rmsnorm_bf16_kernel and the RoPE kernels use neither: they round with
+// the __float2bfloat16 intrinsic, which treats NaN differently (the
+// integer formula can carry an all-ones NaN payload into the sign bit).
+// ---------------------------------------------------------------------------
+
+__device__ __forceinline__ float bf16_to_f32(uint16_t h) {
+  return __uint_as_float((uint32_t)h << 16);
+}
+
+// truncation (keep the high 16 bits) — byte-exact with the wire codec
+// in client_amd.utils.serialize_bf16_tensor (reference semantics:
+// utils/__init__.py:294-330)
+__device__ __forceinline__ uint16_t f32_to_bf16_trunc(float f) {
+  return (uint16_t)(__float_as_uint(f) >> 16);
+}
+
+// round-to-nearest-even (matches torch float->bf16 casts)
+__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
+  uint32_t u = __float_as_uint(f);
+  u += 0x7FFF + ((u >> 16) & 1);
+  return (uint16_t)(u >> 16);
+}
+
+// the two bf16 halves of a packed u32 (low half = lower address)
+__device__ __forceinline__ float bf16x2_lo(uint32_t w) {
+  return __uint_as_float((w & 0xFFFFu) << 16);
+}
+__device__ __forceinline__ float bf16x2_hi(uint32_t w) {
+  return __uint_as_float(w & 0xFFFF0000u);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// Kernels
+// Streaming casts
 // ---------------------------------------------------------------------------
 
-// fp32 -> bf16 by truncation (keep high 16 bits) — byte-exact with the
-// wire codec in client_amd.utils.serialize_bf16_tensor (reference
-// semantics: utils/__init__.py:294-330). Vectorized 8 elems/lane:
-// 32 B in, 16 B out per lane.
-extern "C" __global__ void cast_fp32_bf16_kernel(const uint32_t* __restrict__ src,
-                                                 uint16_t* __restrict__ dst,
-                                                 long n) {
-  long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x) * 8;
-  long stride = (long)gridDim.x * blockDim.x * 8;
-  for (long i = i0; i + 8 <= n; i += stride) {
-    const uint4 a = *reinterpret_cast<const uint4*>(src + i);
-    const uint4 b = *reinterpret_cast<const uint4*>(src + i + 4);
-    uint16_t out[8];
-    out[0] = (uint16_t)(a.x >> 16);
-    out[1] = (uint16_t)(a.y >> 16);
-    out[2] = (uint16_t)(a.z >> 16);
-    out[3] = (uint16_t)(a.w >> 16);
-    out[4] = (uint16_t)(b.x >> 16);
-    out[5] = (uint16_t)(b.y >> 16);
-    out[6] = (uint16_t)(b.z >> 16);
-    out[7] = (uint16_t)(b.w >> 16);
-    *reinterpret_cast<uint4*>(dst + i) = *reinterpret_cast<uint4*>(out);
+namespace {
+
+// A conversion trait names the source and destination element types,
+// the per-element convert, and how many elements a lane moves per
+// iteration of the vector kernel.
+
+// fp32 -> bf16 by truncation. 16 elems/lane (64 B loads, 32 B stores
+// per lane per iteration) — measured against an 8-elem kernel on
+// hardware.
+struct CastF32ToBf16 {
+  using Src = float;
+  using Dst = uint16_t;
+  static constexpr int kPerLane = 16;
+  static __device__ __forceinline__ Dst convert(Src v) {
+    return f32_to_bf16_trunc(v);
   }
-  // tail (grid-stride tail handling: only the lanes owning the ragged end)
-  long tail_start = (n / 8) * 8;
-  long ti = tail_start + (blockIdx.x * blockDim.x + threadIdx.x);
-  if (ti < n && (blockIdx.x * blockDim.x + threadIdx.x) < 8) {
-    dst[ti] = (uint16_t)(src[ti] >> 16);
-  }
-}
+};
 
 // bf16 -> fp32 by zero-extension (wire-exact inverse).
-extern "C" __global__ void cast_bf16_fp32_kernel(const uint16_t* __restrict__ src,
-                                                 uint32_t* __restrict__ dst,
-                                                 long n) {
-  long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x) * 8;
-  long stride = (long)gridDim.x * blockDim.x * 8;
-  for (long i = i0; i + 8 <= n; i += stride) {
-    const uint4 a = *reinterpret_cast<const uint4*>(src + i);  // 8 bf16
-    const uint16_t* s = reinterpret_cast<const uint16_t*>(&a);
-    uint4 lo, hi;
-    lo.x = (uint32_t)s[0] << 16;
-    lo.y = (uint32_t)s[1] << 16;
-    lo.z = (uint32_t)s[2] << 16;
-    lo.w = (uint32_t)s[3] << 16;
-    hi.x = (uint32_t)s[4] << 16;
-    hi.y = (uint32_t)s[5] << 16;
-    hi.z = (uint32_t)s[6] << 16;
-    hi.w = (uint32_t)s[7] << 16;
-    *reinterpret_cast<uint4*>(dst + i) = lo;
-    *reinterpret_cast<uint4*>(dst + i + 4) = hi;
+struct CastBf16ToF32 {
+  using Src = uint16_t;
+  using Dst = float;
+  static constexpr int kPerLane = 8;
+  static __device__ __forceinline__ Dst convert(Src v) {
+    return bf16_to_f32(v);
   }
-  long tail_start = (n / 8) * 8;
-  long ti = tail_start + (blockIdx.x * blockDim.x + threadIdx.x);
-  if (ti < n && (blockIdx.x * blockDim.x + threadIdx.x) < 8) {
-    dst[ti] = (uint32_t)src[ti] << 16;
-  }
-}
-
-// 16-elem/lane unpack variant (mirrors the pack-kernel A/B win)
-extern "C" __global__ void cast_bf16_fp32_v2_kernel(
-    const uint16_t* __restrict__ src, uint32_t* __restrict__ dst, long n) {
-  long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x) * 16;
-  long stride = (long)gridDim.x * blockDim.x * 16;
-  for (long i = i0; i + 16 <= n; i += stride) {
-    uint4 a[2];
-    a[0] = *reinterpret_cast<const uint4*>(src + i);
-    a[1] = *reinterpret_cast<const uint4*>(src + i + 8);
-    const uint16_t* e = reinterpret_cast<const uint16_t*>(a);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      uint4 o;
-      o.x = (uint32_t)e[4 * j + 0] << 16;
-      o.y = (uint32_t)e[4 * j + 1] << 16;
-      o.z = (uint32_t)e[4 * j + 2] << 16;
-      o.w = (uint32_t)e[4 * j + 3] << 16;
-      *reinterpret_cast<uint4*>(dst + i + 4 * j) = o;
-    }
-  }
-  long tail_start = (n / 16) * 16;
-  long ti = tail_start + (blockIdx.x * blockDim.x + threadIdx.x);
-  if (ti < n && (blockIdx.x * blockDim.x + threadIdx.x) < 16) {
-    dst[ti] = (uint32_t)src[ti] << 16;
-  }
-}
+};
 
 // fp32 -> fp8 e4m3 (OCP fn, the CDNA4-native format — NOT MI300X fnuz;
 // cdna_hip_programming.md §4). RNE via the __hip_fp8_e4m3 HW convert.
@@ -123,302 +104,170 @@ extern "C" __global__ void cast_bf16_fp32_v2_kernel(
 //   - NaN and +-Inf pass through the clamp and give a NaN code
 //     ((code & 0x7F) == 0x7F);
 //   - the sign of a zero result is preserved.
-extern "C" __global__ void cast_fp32_fp8e4m3_kernel(const float* __restrict__ src,
-                                                    uint8_t* __restrict__ dst,
-                                                    long n) {
-  long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x) * 8;
-  long stride = (long)gridDim.x * blockDim.x * 8;
-  for (long i = i0; i + 8 <= n; i += stride) {
-    const float4 a = *reinterpret_cast<const float4*>(src + i);
-    const float4 b = *reinterpret_cast<const float4*>(src + i + 4);
-    uint8_t out[8];
-    out[0] = __hip_fp8_e4m3(a.x).__x;
-    out[1] = __hip_fp8_e4m3(a.y).__x;
-    out[2] = __hip_fp8_e4m3(a.z).__x;
-    out[3] = __hip_fp8_e4m3(a.w).__x;
-    out[4] = __hip_fp8_e4m3(b.x).__x;
-    out[5] = __hip_fp8_e4m3(b.y).__x;
-    out[6] = __hip_fp8_e4m3(b.z).__x;
-    out[7] = __hip_fp8_e4m3(b.w).__x;
-    *reinterpret_cast<uint64_t*>(dst + i) = *reinterpret_cast<uint64_t*>(out);
+struct CastF32ToFp8 {
+  using Src = float;
+  using Dst = uint8_t;
+  static constexpr int kPerLane = 8;
+  static __device__ __forceinline__ Dst convert(Src v) {
+    return __hip_fp8_e4m3(v).__x;
   }
-  long tail_start = (n / 8) * 8;
+};
+
+struct CastFp8ToF32 {
+  using Src = uint8_t;
+  using Dst = float;
+  static constexpr int kPerLane = 8;
+  static __device__ __forceinline__ Dst convert(Src v) {
+    __hip_fp8_e4m3 e;
+    e.__x = v;
+    return float(e);
+  }
+};
+
+// moves BYTES between a lane's registers and global memory in 16-byte
+// accesses (one 8-byte access for the 8 x fp8 side)
+template <int BYTES>
+__device__ __forceinline__ void copy_wide(void* dst, const void* src) {
+  if constexpr (BYTES == 8) {
+    *reinterpret_cast<uint64_t*>(dst) = *reinterpret_cast<const uint64_t*>(src);
+  } else {
+    static_assert(BYTES % 16 == 0, "whole 16-byte vectors");
+#pragma unroll
+    for (int k = 0; k < BYTES / 16; ++k)
+      reinterpret_cast<uint4*>(dst)[k] = reinterpret_cast<const uint4*>(src)[k];
+  }
+}
+
+// Vector path (src and dst 16-byte aligned): grid-stride over groups of
+// kPerLane elements, then the first lanes of the grid do the ragged tail.
+template <typename C>
+__device__ __forceinline__ void cast_vec_body(
+    const typename C::Src* __restrict__ src,
+    typename C::Dst* __restrict__ dst, long n) {
+  constexpr int W = C::kPerLane;
+  long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x) * W;
+  long stride = (long)gridDim.x * blockDim.x * W;
+  for (long i = i0; i + W <= n; i += stride) {
+    alignas(16) typename C::Src in[W];
+    alignas(16) typename C::Dst out[W];
+    copy_wide<W * sizeof(typename C::Src)>(in, src + i);
+#pragma unroll
+    for (int j = 0; j < W; ++j) out[j] = C::convert(in[j]);
+    copy_wide<W * sizeof(typename C::Dst)>(dst + i, out);
+  }
+  // tail (grid-stride tail handling: only the lanes owning the ragged end)
+  long tail_start = (n / W) * W;
   long ti = tail_start + (blockIdx.x * blockDim.x + threadIdx.x);
-  if (ti < n && (blockIdx.x * blockDim.x + threadIdx.x) < 8) {
-    dst[ti] = __hip_fp8_e4m3(src[ti]).__x;
+  if (ti < n && (blockIdx.x * blockDim.x + threadIdx.x) < W) {
+    dst[ti] = C::convert(src[ti]);
   }
 }
 
-extern "C" __global__ void cast_fp8e4m3_fp32_kernel(const uint8_t* __restrict__ src,
-                                                    float* __restrict__ dst,
-                                                    long n) {
-  long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x) * 8;
-  long stride = (long)gridDim.x * blockDim.x * 8;
-  for (long i = i0; i + 8 <= n; i += stride) {
-    uint64_t packed = *reinterpret_cast<const uint64_t*>(src + i);
-    const uint8_t* s = reinterpret_cast<const uint8_t*>(&packed);
-    float4 lo, hi;
-    __hip_fp8_e4m3 v;
-    v.__x = s[0]; lo.x = float(v);
-    v.__x = s[1]; lo.y = float(v);
-    v.__x = s[2]; lo.z = float(v);
-    v.__x = s[3]; lo.w = float(v);
-    v.__x = s[4]; hi.x = float(v);
-    v.__x = s[5]; hi.y = float(v);
-    v.__x = s[6]; hi.z = float(v);
-    v.__x = s[7]; hi.w = float(v);
-    *reinterpret_cast<float4*>(dst + i) = lo;
-    *reinterpret_cast<float4*>(dst + i + 4) = hi;
-  }
-  long tail_start = (n / 8) * 8;
-  long ti = tail_start + (blockIdx.x * blockDim.x + threadIdx.x);
-  if (ti < n && (blockIdx.x * blockDim.x + threadIdx.x) < 8) {
-    __hip_fp8_e4m3 v;
-    v.__x = src[ti];
-    dst[ti] = float(v);
-  }
-}
-
-// A/B variant: 16 elems/lane (64 B loads, 32 B stores per lane per
-// iteration) — measured against the 8-elem kernel on hardware.
-extern "C" __global__ void cast_fp32_bf16_v2_kernel(
-    const uint32_t* __restrict__ src, uint16_t* __restrict__ dst, long n) {
-  long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x) * 16;
-  long stride = (long)gridDim.x * blockDim.x * 16;
-  for (long i = i0; i + 16 <= n; i += stride) {
-    uint4 a[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      a[j] = *reinterpret_cast<const uint4*>(src + i + 4 * j);
-    uint16_t out[16];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      out[4 * j + 0] = (uint16_t)(a[j].x >> 16);
-      out[4 * j + 1] = (uint16_t)(a[j].y >> 16);
-      out[4 * j + 2] = (uint16_t)(a[j].z >> 16);
-      out[4 * j + 3] = (uint16_t)(a[j].w >> 16);
-    }
-    *reinterpret_cast<uint4*>(dst + i) = *reinterpret_cast<uint4*>(out);
-    *reinterpret_cast<uint4*>(dst + i + 8) =
-        *reinterpret_cast<uint4*>(out + 8);
-  }
-  long tail_start = (n / 16) * 16;
-  long ti = tail_start + (blockIdx.x * blockDim.x + threadIdx.x);
-  if (ti < n && (blockIdx.x * blockDim.x + threadIdx.x) < 16) {
-    dst[ti] = (uint16_t)(src[ti] >> 16);
-  }
-}
-
-// A/B variant 3: 16 elems/lane with nontemporal loads/stores (the
-// packed stream is written once and read by a different consumer —
-// bypassing L2 may help at HBM-bound sizes).
-extern "C" __global__ void cast_fp32_bf16_v3_kernel(
-    const uint32_t* __restrict__ src, uint16_t* __restrict__ dst, long n) {
-  // clang's nontemporal builtins need ext_vector types, not the HIP
-  // vector structs
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-  long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x) * 16;
-  long stride = (long)gridDim.x * blockDim.x * 16;
-  for (long i = i0; i + 16 <= n; i += stride) {
-    u32x4 a[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      a[j] = __builtin_nontemporal_load(
-          reinterpret_cast<const u32x4*>(src + i + 4 * j));
-    uint16_t out[16];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      out[4 * j + 0] = (uint16_t)(a[j].x >> 16);
-      out[4 * j + 1] = (uint16_t)(a[j].y >> 16);
-      out[4 * j + 2] = (uint16_t)(a[j].z >> 16);
-      out[4 * j + 3] = (uint16_t)(a[j].w >> 16);
-    }
-    __builtin_nontemporal_store(*reinterpret_cast<u32x4*>(out),
-                                reinterpret_cast<u32x4*>(dst + i));
-    __builtin_nontemporal_store(*reinterpret_cast<u32x4*>(out + 8),
-                                reinterpret_cast<u32x4*>(dst + i + 8));
-  }
-  long tail_start = (n / 16) * 16;
-  long ti = tail_start + (blockIdx.x * blockDim.x + threadIdx.x);
-  if (ti < n && (blockIdx.x * blockDim.x + threadIdx.x) < 16) {
-    dst[ti] = (uint16_t)(src[ti] >> 16);
-  }
-}
-
-// Fused RMSNorm for bf16 rows: out = x * rsqrt(mean(x^2)+eps) * w,
-// computed in fp32 (byte-compatible with the torch reference sequence
-// float() -> pow/mean/rsqrt -> mul -> to(bf16), which launches ~7
-// kernels; this is one). One workgroup per row; dim must be a multiple
-// of 8 for the vectorized loads (4096/1024/... in practice).
-extern "C" __global__ void rmsnorm_bf16_kernel(
-    const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
-    uint16_t* __restrict__ out, int dim, float eps) {
-  const int row = blockIdx.x;
-  const uint16_t* xr = x + (long)row * dim;
-  uint16_t* outr = out + (long)row * dim;
-  float acc = 0.f;
-  for (int i = threadIdx.x * 8; i < dim; i += blockDim.x * 8) {
-    uint4 v = *reinterpret_cast<const uint4*>(xr + i);
-    const uint16_t* e = reinterpret_cast<const uint16_t*>(&v);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float f = __uint_as_float((uint32_t)e[j] << 16);
-      acc += f * f;
-    }
-  }
-  // wave + LDS reduction (64-wide waves)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-  __shared__ float warp_sums[16];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  if (lane == 0) warp_sums[wave] = acc;
-  __syncthreads();
-  const int n_waves = (blockDim.x + 63) >> 6;
-  if (threadIdx.x == 0) {
-    float total = 0.f;
-    for (int i = 0; i < n_waves; ++i) total += warp_sums[i];
-    warp_sums[0] = rsqrtf(total / dim + eps);
-  }
-  __syncthreads();
-  const float scale = warp_sums[0];
-  for (int i = threadIdx.x * 8; i < dim; i += blockDim.x * 8) {
-    uint4 v = *reinterpret_cast<const uint4*>(xr + i);
-    uint4 wv = *reinterpret_cast<const uint4*>(w + i);
-    const uint16_t* e = reinterpret_cast<const uint16_t*>(&v);
-    const uint16_t* we = reinterpret_cast<const uint16_t*>(&wv);
-    uint16_t o[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float f = __uint_as_float((uint32_t)e[j] << 16);
-      float wf = __uint_as_float((uint32_t)we[j] << 16);
-      o[j] = __bfloat16_as_ushort(__float2bfloat16(f * scale * wf));
-    }
-    *reinterpret_cast<uint4*>(outr + i) = *reinterpret_cast<uint4*>(o);
-  }
-}
-
-// Fused decode-step RoPE for bf16 q AND k in one launch, with per-row
-// positions (continuous batching): q [b, hq, d], k [b, hk, d]
-// contiguous (s=1), cos/sin tables [max_seq, d/2] fp32, pos [b] int64.
-// Replaces ~8 slicing/elementwise launches per projection.
-extern "C" __global__ void rope_decode_bf16_kernel(
-    uint16_t* __restrict__ q, uint16_t* __restrict__ k,
-    const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
-    const long* __restrict__ pos, int b, int hq, int hk, int d) {
-  const int half = d / 2;
-  const long total = (long)b * (hq + hk) * half;
-  long i = (long)(blockIdx.x * blockDim.x + threadIdx.x);
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    long rem = i;
-    const int j = (int)(rem % half);  // rotation pair index
-    rem /= half;
-    const int head = (int)(rem % (hq + hk));
-    const int row = (int)(rem / (hq + hk));
-    uint16_t* base = (head < hq)
-                         ? q + ((long)row * hq + head) * d
-                         : k + ((long)row * hk + (head - hq)) * d;
-    const float c = cos_tab[pos[row] * half + j];
-    const float s = sin_tab[pos[row] * half + j];
-    const float x1 = __uint_as_float((uint32_t)base[2 * j] << 16);
-    const float x2 = __uint_as_float((uint32_t)base[2 * j + 1] << 16);
-    base[2 * j] = __bfloat16_as_ushort(__float2bfloat16(x1 * c - x2 * s));
-    base[2 * j + 1] = __bfloat16_as_ushort(__float2bfloat16(x1 * s + x2 * c));
-  }
-}
-
-// RoPE + KV-cache scatter in ONE launch: rotates q (in place) and k
-// (rotated values written straight into the cache at each row's
-// position), and copies v into the cache — removing the two
-// torch index_put launches per layer per decode step (64/step at 32
-// layers; measured 28.9 ms / 5120 calls in the decode profile).
-// ck/cv: [b, hk, cache_len, d]; k/v: [b, hk, d] contiguous.
-extern "C" __global__ void rope_scatter_decode_bf16_kernel(
-    uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
-    const uint16_t* __restrict__ v, uint16_t* __restrict__ ck,
-    uint16_t* __restrict__ cv, const float* __restrict__ cos_tab,
-    const float* __restrict__ sin_tab, const long* __restrict__ pos, int b,
-    int hq, int hk, int d, long cache_len, float q_scale) {
-  const int half = d / 2;
-  const long total = (long)b * (hq + 2 * hk) * half;
-  long i = (long)(blockIdx.x * blockDim.x + threadIdx.x);
-  const long stride = (long)gridDim.x * blockDim.x;
-  for (; i < total; i += stride) {
-    long rem = i;
-    const int j = (int)(rem % half);
-    rem /= half;
-    const int head = (int)(rem % (hq + 2 * hk));
-    const int row = (int)(rem / (hq + 2 * hk));
-    const long p = pos[row];
-    if (head < hq) {  // q: rotate in place (+ folded 1/sqrt(d) scale)
-      uint16_t* base = q + ((long)row * hq + head) * d;
-      const float c = cos_tab[p * half + j];
-      const float s = sin_tab[p * half + j];
-      const float x1 = __uint_as_float((uint32_t)base[2 * j] << 16);
-      const float x2 = __uint_as_float((uint32_t)base[2 * j + 1] << 16);
-      base[2 * j] = __bfloat16_as_ushort(
-          __float2bfloat16((x1 * c - x2 * s) * q_scale));
-      base[2 * j + 1] = __bfloat16_as_ushort(
-          __float2bfloat16((x1 * s + x2 * c) * q_scale));
-    } else if (head < hq + hk) {  // k: rotate -> cache
-      const int h = head - hq;
-      const uint16_t* base = k + ((long)row * hk + h) * d;
-      uint16_t* dst =
-          ck + (((long)row * hk + h) * cache_len + p) * d;
-      const float c = cos_tab[p * half + j];
-      const float s = sin_tab[p * half + j];
-      const float x1 = __uint_as_float((uint32_t)base[2 * j] << 16);
-      const float x2 = __uint_as_float((uint32_t)base[2 * j + 1] << 16);
-      dst[2 * j] =
-          __bfloat16_as_ushort(__float2bfloat16(x1 * c - x2 * s));
-      dst[2 * j + 1] =
-          __bfloat16_as_ushort(__float2bfloat16(x1 * s + x2 * c));
-    } else {  // v: straight copy -> cache
-      const int h = head - hq - hk;
-      const uint16_t* base = v + ((long)row * hk + h) * d;
-      uint16_t* dst =
-          cv + (((long)row * hk + h) * cache_len + p) * d;
-      dst[2 * j] = base[2 * j];
-      dst[2 * j + 1] = base[2 * j + 1];
-    }
-  }
-}
-
-// Scalar fallbacks for pointers not 16-byte aligned (region offsets are
+// Scalar fallback for pointers not 16-byte aligned (region offsets are
 // caller-controlled; hipMalloc bases are 256-B aligned so the vector
 // path is the common case).
-extern "C" __global__ void cast_fp32_bf16_scalar_kernel(
-    const uint32_t* __restrict__ src, uint16_t* __restrict__ dst, long n) {
+template <typename C>
+__device__ __forceinline__ void cast_scalar_body(
+    const typename C::Src* __restrict__ src,
+    typename C::Dst* __restrict__ dst, long n) {
   long i = (long)(blockIdx.x * blockDim.x + threadIdx.x);
   long stride = (long)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) dst[i] = (uint16_t)(src[i] >> 16);
+  for (; i < n; i += stride) dst[i] = C::convert(src[i]);
+}
+
+}  // namespace
+
+// (the fp32 -> bf16 vector kernel keeps the "_v2" of the A/B comparison
+// it won, so profiler tables stay comparable)
+extern "C" __global__ void cast_fp32_bf16_v2_kernel(
+    const float* __restrict__ src, uint16_t* __restrict__ dst, long n) {
+  cast_vec_body<CastF32ToBf16>(src, dst, n);
+}
+
+extern "C" __global__ void cast_fp32_bf16_scalar_kernel(
+    const float* __restrict__ src, uint16_t* __restrict__ dst, long n) {
+  cast_scalar_body<CastF32ToBf16>(src, dst, n);
+}
+
+extern "C" __global__ void cast_bf16_fp32_kernel(
+    const uint16_t* __restrict__ src, float* __restrict__ dst, long n) {
+  cast_vec_body<CastBf16ToF32>(src, dst, n);
 }
 
 extern "C" __global__ void cast_bf16_fp32_scalar_kernel(
-    const uint16_t* __restrict__ src, uint32_t* __restrict__ dst, long n) {
-  long i = (long)(blockIdx.x * blockDim.x + threadIdx.x);
-  long stride = (long)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) dst[i] = (uint32_t)src[i] << 16;
+    const uint16_t* __restrict__ src, float* __restrict__ dst, long n) {
+  cast_scalar_body<CastBf16ToF32>(src, dst, n);
+}
+
+extern "C" __global__ void cast_fp32_fp8e4m3_kernel(
+    const float* __restrict__ src, uint8_t* __restrict__ dst, long n) {
+  cast_vec_body<CastF32ToFp8>(src, dst, n);
 }
 
 extern "C" __global__ void cast_fp32_fp8e4m3_scalar_kernel(
     const float* __restrict__ src, uint8_t* __restrict__ dst, long n) {
-  long i = (long)(blockIdx.x * blockDim.x + threadIdx.x);
-  long stride = (long)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) dst[i] = __hip_fp8_e4m3(src[i]).__x;
+  cast_scalar_body<CastF32ToFp8>(src, dst, n);
+}
+
+extern "C" __global__ void cast_fp8e4m3_fp32_kernel(
+    const uint8_t* __restrict__ src, float* __restrict__ dst, long n) {
+  cast_vec_body<CastFp8ToF32>(src, dst, n);
 }
 
 extern "C" __global__ void cast_fp8e4m3_fp32_scalar_kernel(
     const uint8_t* __restrict__ src, float* __restrict__ dst, long n) {
-  long i = (long)(blockIdx.x * blockDim.x + threadIdx.x);
-  long stride = (long)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    __hip_fp8_e4m3 v;
-    v.__x = src[i];
-    dst[i] = float(v);
-  }
+  cast_scalar_body<CastFp8ToF32>(src, dst, n);
 }
+
+namespace {
+
+// alignment dispatch shared by the four ca_cast_* launchers
+template <typename C>
+hipError_t ca_launch_cast(
+    void (*vec_kernel)(const typename C::Src*, typename C::Dst*, long),
+    void (*scalar_kernel)(const typename C::Src*, typename C::Dst*, long),
+    const void* src, void* dst, long n, hipStream_t stream) {
+  const bool aligned = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
+  const long work = aligned ? (n + C::kPerLane - 1) / C::kPerLane : n;
+  hipLaunchKernelGGL(aligned ? vec_kernel : scalar_kernel,
+                     dim3(ca_grid_for(work)), dim3(256), 0, stream,
+                     (const typename C::Src*)src, (typename C::Dst*)dst, n);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" hipError_t ca_cast_fp32_bf16(const void* src, void* dst, long n,
+                                        hipStream_t stream) {
+  return ca_launch_cast<CastF32ToBf16>(cast_fp32_bf16_v2_kernel,
+                                       cast_fp32_bf16_scalar_kernel, src, dst,
+                                       n, stream);
+}
+
+extern "C" hipError_t ca_cast_bf16_fp32(const void* src, void* dst, long n,
+                                        hipStream_t stream) {
+  return ca_launch_cast<CastBf16ToF32>(cast_bf16_fp32_kernel,
+                                       cast_bf16_fp32_scalar_kernel, src, dst,
+                                       n, stream);
+}
+
+extern "C" hipError_t ca_cast_fp32_fp8e4m3(const void* src, void* dst, long n,
+                                           hipStream_t stream) {
+  return ca_launch_cast<CastF32ToFp8>(cast_fp32_fp8e4m3_kernel,
+                                      cast_fp32_fp8e4m3_scalar_kernel, src,
+                                      dst, n, stream);
+}
+
+extern "C" hipError_t ca_cast_fp8e4m3_fp32(const void* src, void* dst, long n,
+                                           hipStream_t stream) {
+  return ca_launch_cast<CastFp8ToF32>(cast_fp8e4m3_fp32_kernel,
+                                      cast_fp8e4m3_fp32_scalar_kernel, src,
+                                      dst, n, stream);
+}
+
+// ---------------------------------------------------------------------------
+// Strided gather / tiled transpose
+// ---------------------------------------------------------------------------
 
 // Strided -> contiguous gather (up to 4-D), element size 1/2/4/8 bytes.
 // Lifts the reference's "DLPack tensor must be contiguous" restriction
@@ -536,20 +385,102 @@ extern "C" __global__ void transpose_tiled_pair16_kernel(
   }
 }
 
+namespace {
+
+// launches the tiled transpose or the per-element gather for one
+// element type
+template <typename T>
+hipError_t ca_gather_pack_launch(const void* src, void* dst,
+                                 const long* shape, const long* strides,
+                                 bool tiled, hipStream_t stream) {
+  if (!tiled) {
+    const long n = shape[0] * shape[1] * shape[2] * shape[3];
+    hipLaunchKernelGGL((gather_pack_kernel<T>), dim3(ca_grid_for(n)),
+                       dim3(256), 0, stream, (const char*)src, (T*)dst, n,
+                       strides[0], strides[1], strides[2], strides[3],
+                       shape[0], shape[1], shape[2], shape[3]);
+    return hipGetLastError();
+  }
+  const long rows = shape[2], cols = shape[3];
+  dim3 grid((uint32_t)((rows + CA_TILE - 1) / CA_TILE),
+            (uint32_t)((cols + CA_TILE - 1) / CA_TILE),
+            (uint32_t)(shape[0] * shape[1]));
+  bool pair_aligned = false;
+  if constexpr (sizeof(T) == 2) {
+    // pair-per-lane variant restores full bus width for 2-byte
+    // elements (u16 path: 2.3 TB/s; fp32: 4.2). Its u32 accesses
+    // are aligned only for 4-byte-aligned bases and even element
+    // offsets; any odd stride/extent/base takes the u16 kernel.
+    pair_aligned =
+        (((uintptr_t)src | (uintptr_t)dst) & 3) == 0 &&
+        ((strides[3] | strides[0] | strides[1] | cols) & 1) == 0;
+  }
+  if (pair_aligned) {
+    hipLaunchKernelGGL(transpose_tiled_pair16_kernel, grid, dim3(256), 0,
+                       stream, (const uint16_t*)src, (uint16_t*)dst, rows,
+                       cols, strides[3], strides[0], strides[1], shape[1]);
+  } else {
+    hipLaunchKernelGGL((transpose_tiled_kernel<T>), grid, dim3(256), 0,
+                       stream, (const T*)src, (T*)dst, rows, cols, strides[3],
+                       strides[0], strides[1], shape[1]);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" hipError_t ca_gather_pack(const void* src, void* dst,
+                                     int elem_size, const long* shape,
+                                     const long* strides,
+                                     hipStream_t stream) {
+  // shape/strides are 4-element host arrays (leading dims padded)
+  // transpose-like fast path: dim 2 contiguous in the source, innermost
+  // output dim strided -> LDS-tiled transpose (coalesced both ways;
+  // the naive per-element path was 7x off peak on this pattern,
+  // profiles/kernels_rocprof_r01.txt:18)
+  const bool tiled = strides[2] == 1 && strides[3] != 1 && shape[2] >= 16 &&
+                     shape[3] >= 16 && shape[0] * shape[1] <= 65535 &&
+                     (shape[3] + CA_TILE - 1) / CA_TILE <= 65535;
+  switch (elem_size) {
+    case 1:
+      return ca_gather_pack_launch<uint8_t>(src, dst, shape, strides, tiled,
+                                            stream);
+    case 2:
+      return ca_gather_pack_launch<uint16_t>(src, dst, shape, strides, tiled,
+                                             stream);
+    case 4:
+      return ca_gather_pack_launch<uint32_t>(src, dst, shape, strides, tiled,
+                                             stream);
+    case 8:
+      return ca_gather_pack_launch<uint64_t>(src, dst, shape, strides, tiled,
+                                             stream);
+    default:
+      return hipErrorInvalidValue;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Image preprocess
+// ---------------------------------------------------------------------------
+
+namespace {
+
 // Image preprocess: u8 HWC (ih,iw,3) -> bilinear resize (oh,ow) ->
 // normalize -> planar CHW fp32 (or bf16). One thread per output pixel
 // computes all 3 channels (reads coalesce along ow; the 4 source pixels
 // hit L1/L2 for neighbors). Modes: 0 = raw /1, 1 = INCEPTION
 // (x/127.5 - 1), 2 = VGG (x - mean_c), matching image_client.cc:86-190.
-extern "C" __global__ void image_preprocess_kernel(
-    const uint8_t* __restrict__ src, float* __restrict__ dst,
-    int ih, int iw, int oh, int ow, int mode, int out_bf16,
-    float m0, float m1, float m2, float s0, float s1, float s2) {
-  long n = (long)oh * ow;
-  long i = (long)(blockIdx.x * blockDim.x + threadIdx.x);
-  long stride = (long)gridDim.x * blockDim.x;
-  float scale_h = (float)ih / oh;
-  float scale_w = (float)iw / ow;
+//
+// One image: simg is its u8 input, dimg / dimg16 the same CHW output
+// viewed as fp32 / bf16, n = oh * ow its pixel count; the grid's x
+// dimension strides over pixels starting at i.
+__device__ __forceinline__ void image_preprocess_body(
+    const uint8_t* __restrict__ simg, float* __restrict__ dimg,
+    uint16_t* __restrict__ dimg16, const long n, long i, const long stride,
+    int ih, int iw, int oh, int ow, int mode, int out_bf16, float m0,
+    float m1, float m2, float s0, float s1, float s2) {
+  const float scale_h = (float)ih / oh;
+  const float scale_w = (float)iw / ow;
   for (; i < n; i += stride) {
     int oy = i / ow;
     int ox = i % ow;
@@ -565,10 +496,10 @@ extern "C" __global__ void image_preprocess_kernel(
     float wx = fx - floorf(fx);
     if (fy < 0) wy = 0.f;
     if (fx < 0) wx = 0.f;
-    const uint8_t* p00 = src + ((long)y0 * iw + x0) * 3;
-    const uint8_t* p01 = src + ((long)y0 * iw + x1) * 3;
-    const uint8_t* p10 = src + ((long)y1 * iw + x0) * 3;
-    const uint8_t* p11 = src + ((long)y1 * iw + x1) * 3;
+    const uint8_t* p00 = simg + ((long)y0 * iw + x0) * 3;
+    const uint8_t* p01 = simg + ((long)y0 * iw + x1) * 3;
+    const uint8_t* p10 = simg + ((long)y1 * iw + x0) * 3;
+    const uint8_t* p11 = simg + ((long)y1 * iw + x1) * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       float v = (1 - wy) * ((1 - wx) * p00[c] + wx * p01[c]) +
@@ -582,17 +513,266 @@ extern "C" __global__ void image_preprocess_kernel(
       } else {
         v = (v - mean) * sc;
       }
-      long out_idx = (long)c * n + i;  // CHW
+      long out_idx = (long)c * n + i;  // CHW within the image
       if (out_bf16) {
-        reinterpret_cast<uint16_t*>(dst)[out_idx] =
-            (uint16_t)(__float_as_uint(v) >> 16);
+        dimg16[out_idx] = f32_to_bf16_trunc(v);
       } else {
-        dst[out_idx] = v;
+        dimg[out_idx] = v;
       }
     }
   }
 }
 
+}  // namespace
+
+// One image per launch. Kept apart from the batched kernel below: run
+// through that one, a single image pays the blockIdx.y offset
+// arithmetic in the prologue, +0.24-0.28 us on a 2.9-3.4 us kernel
+// (docs/PERFORMANCE.md, "Kernel file deduplication").
+extern "C" __global__ void image_preprocess_kernel(
+    const uint8_t* __restrict__ src, float* __restrict__ dst,
+    int ih, int iw, int oh, int ow, int mode, int out_bf16,
+    float m0, float m1, float m2, float s0, float s1, float s2) {
+  const long n = (long)oh * ow;
+  const long i = (long)(blockIdx.x * blockDim.x + threadIdx.x);
+  const long stride = (long)gridDim.x * blockDim.x;
+  image_preprocess_body(src, dst, reinterpret_cast<uint16_t*>(dst), n, i,
+                        stride, ih, iw, oh, ow, mode, out_bf16, m0, m1, m2,
+                        s0, s1, s2);
+}
+
+extern "C" hipError_t ca_image_preprocess(const void* src, void* dst, int ih,
+                                          int iw, int oh, int ow, int mode,
+                                          int out_bf16, const float* mean,
+                                          const float* stdev,
+                                          hipStream_t stream) {
+  hipLaunchKernelGGL(image_preprocess_kernel,
+                     dim3(ca_grid_for((long)oh * ow)), dim3(256), 0, stream,
+                     (const uint8_t*)src, (float*)dst, ih, iw, oh, ow, mode,
+                     out_bf16, mean[0], mean[1], mean[2], stdev[0], stdev[1],
+                     stdev[2]);
+  return hipGetLastError();
+}
+
+// Batched variant: N same-sized images in one launch (u8 HWC stacked
+// contiguously -> NCHW). The single-image kernel is launch-bound at
+// high request rates (~27 us/image vs ~2-3 us of kernel time for
+// 224x224 — profiles/kernels_rocprof_r01.txt:19); the batch amortizes
+// one launch over the whole request. blockIdx.y = image index (grid.y
+// caps at 65535 — far above any sane batch).
+extern "C" __global__ void image_preprocess_batched_kernel(
+    const uint8_t* __restrict__ src, float* __restrict__ dst, int ih, int iw,
+    int oh, int ow, int mode, int out_bf16, float m0, float m1, float m2,
+    float s0, float s1, float s2) {
+  const long in_img = (long)ih * iw * 3;
+  const long n = (long)oh * ow;
+  const uint8_t* simg = src + (long)blockIdx.y * in_img;
+  float* dimg = dst + (long)blockIdx.y * 3 * n;
+  uint16_t* dimg16 =
+      reinterpret_cast<uint16_t*>(dst) + (long)blockIdx.y * 3 * n;
+  const long i = (long)(blockIdx.x * blockDim.x + threadIdx.x);
+  const long stride = (long)gridDim.x * blockDim.x;
+  image_preprocess_body(simg, dimg, dimg16, n, i, stride, ih, iw, oh, ow,
+                        mode, out_bf16, m0, m1, m2, s0, s1, s2);
+}
+
+extern "C" hipError_t ca_image_preprocess_batched(
+    const void* src, void* dst, int n_images, int ih, int iw, int oh, int ow,
+    int mode, int out_bf16, const float* mean, const float* stdev,
+    hipStream_t stream) {
+  if (n_images < 1 || n_images > 65535) return hipErrorInvalidValue;
+  dim3 grid((uint32_t)ca_grid_for((long)oh * ow), (uint32_t)n_images);
+  hipLaunchKernelGGL(image_preprocess_batched_kernel, grid, dim3(256), 0,
+                     stream, (const uint8_t*)src, (float*)dst, ih, iw, oh,
+                     ow, mode, out_bf16, mean[0], mean[1], mean[2], stdev[0],
+                     stdev[1], stdev[2]);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// LLM decode kernels
+// ---------------------------------------------------------------------------
+
+// Fused RMSNorm for bf16 rows: out = x * rsqrt(mean(x^2)+eps) * w,
+// computed in fp32 (byte-compatible with the torch reference sequence
+// float() -> pow/mean/rsqrt -> mul -> to(bf16), which launches ~7
+// kernels; this is one). One workgroup per row; dim must be a multiple
+// of 8 for the vectorized loads (4096/1024/... in practice).
+extern "C" __global__ void rmsnorm_bf16_kernel(
+    const uint16_t* __restrict__ x, const uint16_t* __restrict__ w,
+    uint16_t* __restrict__ out, int dim, float eps) {
+  const int row = blockIdx.x;
+  const uint16_t* xr = x + (long)row * dim;
+  uint16_t* outr = out + (long)row * dim;
+  float acc = 0.f;
+  for (int i = threadIdx.x * 8; i < dim; i += blockDim.x * 8) {
+    uint4 v = *reinterpret_cast<const uint4*>(xr + i);
+    const uint16_t* e = reinterpret_cast<const uint16_t*>(&v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float f = bf16_to_f32(e[j]);
+      acc += f * f;
+    }
+  }
+  // wave + LDS reduction (64-wide waves)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+  __shared__ float warp_sums[16];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  if (lane == 0) warp_sums[wave] = acc;
+  __syncthreads();
+  const int n_waves = (blockDim.x + 63) >> 6;
+  if (threadIdx.x == 0) {
+    float total = 0.f;
+    for (int i = 0; i < n_waves; ++i) total += warp_sums[i];
+    warp_sums[0] = rsqrtf(total / dim + eps);
+  }
+  __syncthreads();
+  const float scale = warp_sums[0];
+  for (int i = threadIdx.x * 8; i < dim; i += blockDim.x * 8) {
+    uint4 v = *reinterpret_cast<const uint4*>(xr + i);
+    uint4 wv = *reinterpret_cast<const uint4*>(w + i);
+    const uint16_t* e = reinterpret_cast<const uint16_t*>(&v);
+    const uint16_t* we = reinterpret_cast<const uint16_t*>(&wv);
+    uint16_t o[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float f = bf16_to_f32(e[j]);
+      float wf = bf16_to_f32(we[j]);
+      o[j] = __bfloat16_as_ushort(__float2bfloat16(f * scale * wf));
+    }
+    *reinterpret_cast<uint4*>(outr + i) = *reinterpret_cast<uint4*>(o);
+  }
+}
+
+extern "C" hipError_t ca_rmsnorm_bf16(const void* x, const void* w, void* out,
+                                      long rows, int dim, float eps,
+                                      hipStream_t stream) {
+  if (dim % 8 != 0) return hipErrorInvalidValue;
+  if (rows == 0) return hipSuccess;  // nothing to do; a zero grid is invalid
+  hipLaunchKernelGGL(rmsnorm_bf16_kernel, dim3((uint32_t)rows), dim3(256), 0,
+                     stream, (const uint16_t*)x, (const uint16_t*)w,
+                     (uint16_t*)out, dim, eps);
+  return hipGetLastError();
+}
+
+namespace {
+
+// Rotates the bf16 pair src[2j], src[2j+1] by the angle (c, s), scales
+// it, and writes it to dst[2j], dst[2j+1] (dst may be src).
+__device__ __forceinline__ void rope_rotate_pair(const uint16_t* src,
+                                                 uint16_t* dst, int j,
+                                                 float c, float s,
+                                                 float scale) {
+  const float x1 = bf16_to_f32(src[2 * j]);
+  const float x2 = bf16_to_f32(src[2 * j + 1]);
+  dst[2 * j] = __bfloat16_as_ushort(__float2bfloat16((x1 * c - x2 * s) * scale));
+  dst[2 * j + 1] =
+      __bfloat16_as_ushort(__float2bfloat16((x1 * s + x2 * c) * scale));
+}
+
+}  // namespace
+
+// Fused decode-step RoPE for bf16 q AND k in one launch, with per-row
+// positions (continuous batching): q [b, hq, d], k [b, hk, d]
+// contiguous (s=1), cos/sin tables [max_seq, d/2] fp32, pos [b] int64.
+// Replaces ~8 slicing/elementwise launches per projection.
+extern "C" __global__ void rope_decode_bf16_kernel(
+    uint16_t* __restrict__ q, uint16_t* __restrict__ k,
+    const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
+    const long* __restrict__ pos, int b, int hq, int hk, int d) {
+  const int half = d / 2;
+  const long total = (long)b * (hq + hk) * half;
+  long i = (long)(blockIdx.x * blockDim.x + threadIdx.x);
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (; i < total; i += stride) {
+    long rem = i;
+    const int j = (int)(rem % half);  // rotation pair index
+    rem /= half;
+    const int head = (int)(rem % (hq + hk));
+    const int row = (int)(rem / (hq + hk));
+    uint16_t* base = (head < hq)
+                         ? q + ((long)row * hq + head) * d
+                         : k + ((long)row * hk + (head - hq)) * d;
+    const float c = cos_tab[pos[row] * half + j];
+    const float s = sin_tab[pos[row] * half + j];
+    rope_rotate_pair(base, base, j, c, s, 1.0f);
+  }
+}
+
+extern "C" hipError_t ca_rope_decode_bf16(void* q, void* k,
+                                          const void* cos_tab,
+                                          const void* sin_tab,
+                                          const void* pos, int b, int hq,
+                                          int hk, int d, hipStream_t stream) {
+  long total = (long)b * (hq + hk) * (d / 2);
+  hipLaunchKernelGGL(rope_decode_bf16_kernel, dim3(ca_grid_for(total)),
+                     dim3(256), 0, stream, (uint16_t*)q, (uint16_t*)k,
+                     (const float*)cos_tab, (const float*)sin_tab,
+                     (const long*)pos, b, hq, hk, d);
+  return hipGetLastError();
+}
+
+// RoPE + KV-cache scatter in ONE launch: rotates q (in place) and k
+// (rotated values written straight into the cache at each row's
+// position), and copies v into the cache — removing the two
+// torch index_put launches per layer per decode step (64/step at 32
+// layers; measured 28.9 ms / 5120 calls in the decode profile).
+// ck/cv: [b, hk, cache_len, d]; k/v: [b, hk, d] contiguous.
+extern "C" __global__ void rope_scatter_decode_bf16_kernel(
+    uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
+    const uint16_t* __restrict__ v, uint16_t* __restrict__ ck,
+    uint16_t* __restrict__ cv, const float* __restrict__ cos_tab,
+    const float* __restrict__ sin_tab, const long* __restrict__ pos, int b,
+    int hq, int hk, int d, long cache_len, float q_scale) {
+  const int half = d / 2;
+  const long total = (long)b * (hq + 2 * hk) * half;
+  long i = (long)(blockIdx.x * blockDim.x + threadIdx.x);
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (; i < total; i += stride) {
+    long rem = i;
+    const int j = (int)(rem % half);
+    rem /= half;
+    const int head = (int)(rem % (hq + 2 * hk));
+    const int row = (int)(rem / (hq + 2 * hk));
+    const long p = pos[row];
+    if (head < hq) {  // q: rotate in place (+ folded 1/sqrt(d) scale)
+      uint16_t* base = q + ((long)row * hq + head) * d;
+      rope_rotate_pair(base, base, j, cos_tab[p * half + j],
+                       sin_tab[p * half + j], q_scale);
+    } else if (head < hq + hk) {  // k: rotate -> cache
+      const int h = head - hq;
+      const uint16_t* base = k + ((long)row * hk + h) * d;
+      uint16_t* dst =
+          ck + (((long)row * hk + h) * cache_len + p) * d;
+      rope_rotate_pair(base, dst, j, cos_tab[p * half + j],
+                       sin_tab[p * half + j], 1.0f);
+    } else {  // v: straight copy -> cache
+      const int h = head - hq - hk;
+      const uint16_t* base = v + ((long)row * hk + h) * d;
+      uint16_t* dst =
+          cv + (((long)row * hk + h) * cache_len + p) * d;
+      dst[2 * j] = base[2 * j];
+      dst[2 * j + 1] = base[2 * j + 1];
+    }
+  }
+}
+
+extern "C" hipError_t ca_rope_scatter_decode_bf16(
+    void* q, const void* k, const void* v, void* ck, void* cv,
+    const void* cos_tab, const void* sin_tab, const void* pos, int b,
+    int hq, int hk, int d, long cache_len, float q_scale,
+    hipStream_t stream) {
+  long total = (long)b * (hq + 2 * hk) * (d / 2);
+  hipLaunchKernelGGL(rope_scatter_decode_bf16_kernel,
+                     dim3(ca_grid_for(total)), dim3(256), 0, stream,
+                     (uint16_t*)q, (const uint16_t*)k, (const uint16_t*)v,
+                     (uint16_t*)ck, (uint16_t*)cv, (const float*)cos_tab,
+                     (const float*)sin_tab, (const long*)pos, b, hq, hk, d,
+                     cache_len, q_scale);
+  return hipGetLastError();
+}
 
 // Skinny decode GEMM: y[8, N] = x[8, K] @ W[N, K]^T, bf16 in/out,
 // fp32 accumulate. The decode batch is tiny (8 rows), so the GEMM is
@@ -647,8 +827,7 @@ decode_gemm_bf16_kernel(const uint16_t* __restrict__ x,
           const uint16_t* we = reinterpret_cast<const uint16_t*>(&wv);
           float wf[8];
 #pragma unroll
-          for (int j = 0; j < 8; ++j)
-            wf[j] = __uint_as_float((uint32_t)we[j] << 16);
+          for (int j = 0; j < 8; ++j) wf[j] = bf16_to_f32(we[j]);
 #pragma unroll
           for (int m = 0; m < DG_M; ++m) {
             const uint16_t* xr = xs + m * DG_KC + k0;
@@ -657,7 +836,7 @@ decode_gemm_bf16_kernel(const uint16_t* __restrict__ x,
             float s = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-              s = fmaf(__uint_as_float((uint32_t)xe[j] << 16), wf[j], s);
+              s = fmaf(bf16_to_f32(xe[j]), wf[j], s);
             acc[m] += s;
           }
         }
@@ -671,11 +850,7 @@ decode_gemm_bf16_kernel(const uint16_t* __restrict__ x,
         float v = acc[m];
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-        if (lane == 0) {
-          uint32_t u = __float_as_uint(v);
-          u += 0x7FFF + ((u >> 16) & 1);  // RNE to bf16
-          y[(long)m * N + n] = (uint16_t)(u >> 16);
-        }
+        if (lane == 0) y[(long)m * N + n] = f32_to_bf16_rne(v);
       }
     }
   }
@@ -699,300 +874,96 @@ extern "C" hipError_t ca_decode_gemm_bf16(const void* x, const void* w,
 }
 
 // ---------------------------------------------------------------------------
-// C-ABI launchers (alignment dispatch included). Return hipError_t.
+// ResNet epilogues: per-channel bias (+ residual) (+ ReLU) over bf16
 // ---------------------------------------------------------------------------
-
-extern "C" hipError_t ca_cast_fp32_bf16(const void* src, void* dst, long n,
-                                        hipStream_t stream) {
-  auto s = reinterpret_cast<uintptr_t>(src);
-  auto d = reinterpret_cast<uintptr_t>(dst);
-  if ((s | d) & 15) {
-    hipLaunchKernelGGL(cast_fp32_bf16_scalar_kernel, dim3(ca_grid_for(n)),
-                       dim3(256), 0, stream, (const uint32_t*)src,
-                       (uint16_t*)dst, n);
-  } else {
-    hipLaunchKernelGGL(cast_fp32_bf16_v2_kernel,
-                       dim3(ca_grid_for((n + 15) / 16)), dim3(256), 0, stream,
-                       (const uint32_t*)src, (uint16_t*)dst, n);
-  }
-  return hipGetLastError();
-}
-
-extern "C" hipError_t ca_cast_bf16_fp32(const void* src, void* dst, long n,
-                                        hipStream_t stream) {
-  auto s = reinterpret_cast<uintptr_t>(src);
-  auto d = reinterpret_cast<uintptr_t>(dst);
-  if ((s | d) & 15) {
-    hipLaunchKernelGGL(cast_bf16_fp32_scalar_kernel, dim3(ca_grid_for(n)),
-                       dim3(256), 0, stream, (const uint16_t*)src,
-                       (uint32_t*)dst, n);
-  } else {
-    hipLaunchKernelGGL(cast_bf16_fp32_kernel, dim3(ca_grid_for((n + 7) / 8)),
-                       dim3(256), 0, stream, (const uint16_t*)src,
-                       (uint32_t*)dst, n);
-  }
-  return hipGetLastError();
-}
-
-extern "C" hipError_t ca_cast_fp32_fp8e4m3(const void* src, void* dst, long n,
-                                           hipStream_t stream) {
-  auto s = reinterpret_cast<uintptr_t>(src);
-  auto d = reinterpret_cast<uintptr_t>(dst);
-  if ((s | d) & 15) {
-    hipLaunchKernelGGL(cast_fp32_fp8e4m3_scalar_kernel, dim3(ca_grid_for(n)),
-                       dim3(256), 0, stream, (const float*)src,
-                       (uint8_t*)dst, n);
-  } else {
-    hipLaunchKernelGGL(cast_fp32_fp8e4m3_kernel,
-                       dim3(ca_grid_for((n + 7) / 8)), dim3(256), 0, stream,
-                       (const float*)src, (uint8_t*)dst, n);
-  }
-  return hipGetLastError();
-}
-
-extern "C" hipError_t ca_cast_fp8e4m3_fp32(const void* src, void* dst, long n,
-                                           hipStream_t stream) {
-  auto s = reinterpret_cast<uintptr_t>(src);
-  auto d = reinterpret_cast<uintptr_t>(dst);
-  if ((s | d) & 15) {
-    hipLaunchKernelGGL(cast_fp8e4m3_fp32_scalar_kernel, dim3(ca_grid_for(n)),
-                       dim3(256), 0, stream, (const uint8_t*)src,
-                       (float*)dst, n);
-  } else {
-    hipLaunchKernelGGL(cast_fp8e4m3_fp32_kernel,
-                       dim3(ca_grid_for((n + 7) / 8)), dim3(256), 0, stream,
-                       (const uint8_t*)src, (float*)dst, n);
-  }
-  return hipGetLastError();
-}
 
 namespace {
 
-template <typename T>
-hipError_t ca_transpose_tiled_launch(const void* src, void* dst,
-                                     const long* shape, const long* strides,
-                                     hipStream_t stream) {
-  const long rows = shape[2], cols = shape[3];
-  dim3 grid((uint32_t)((rows + CA_TILE - 1) / CA_TILE),
-            (uint32_t)((cols + CA_TILE - 1) / CA_TILE),
-            (uint32_t)(shape[0] * shape[1]));
-  hipLaunchKernelGGL((transpose_tiled_kernel<T>), grid, dim3(256), 0, stream,
-                     (const T*)src, (T*)dst, rows, cols, strides[3],
-                     strides[0], strides[1], shape[1]);
-  return hipGetLastError();
+// optional ReLU, then RNE back to bf16
+__device__ __forceinline__ uint16_t epilogue_finish(float f, int do_relu) {
+  if (do_relu && f < 0.f) f = 0.f;
+  return f32_to_bf16_rne(f);
+}
+
+// One packed pair of bf16 elements through the epilogue: x (and the
+// residual pair when has_res) with the biases of its two elements.
+// The addition order (x + residual) + bias matches the torch reference
+// sequence exactly (fp32 add is non-associative; a different order
+// flips RNE boundary cases).
+__device__ __forceinline__ uint32_t epilogue_pair(uint32_t xw, uint32_t rw,
+                                                  bool has_res, float b_lo,
+                                                  float b_hi, int do_relu) {
+  float lo = bf16x2_lo(xw);
+  float hi = bf16x2_hi(xw);
+  if (has_res) {
+    lo += bf16x2_lo(rw);
+    hi += bf16x2_hi(rw);
+  }
+  return (uint32_t)epilogue_finish(lo + b_lo, do_relu) |
+         ((uint32_t)epilogue_finish(hi + b_hi, do_relu) << 16);
+}
+
+// the same for one element of a ragged end (res may be null)
+__device__ __forceinline__ uint16_t epilogue_one(const uint16_t* x,
+                                                 const uint16_t* res, long i,
+                                                 float b, int do_relu) {
+  float f = bf16_to_f32(x[i]);
+  if (res) f += bf16_to_f32(res[i]);
+  return epilogue_finish(f + b, do_relu);
 }
 
 }  // namespace
 
-extern "C" hipError_t ca_gather_pack(const void* src, void* dst,
-                                     int elem_size, const long* shape,
-                                     const long* strides,
-                                     hipStream_t stream) {
-  // shape/strides are 4-element host arrays (leading dims padded)
-  long n = shape[0] * shape[1] * shape[2] * shape[3];
-  // transpose-like fast path: dim 2 contiguous in the source, innermost
-  // output dim strided -> LDS-tiled transpose (coalesced both ways;
-  // the naive per-element path was 7x off peak on this pattern,
-  // profiles/kernels_rocprof_r01.txt:18)
-  if (strides[2] == 1 && strides[3] != 1 && shape[2] >= 16 &&
-      shape[3] >= 16 && shape[0] * shape[1] <= 65535 &&
-      (shape[3] + CA_TILE - 1) / CA_TILE <= 65535) {
-    switch (elem_size) {
-      case 1:
-        return ca_transpose_tiled_launch<uint8_t>(src, dst, shape, strides,
-                                                  stream);
-      case 2: {
-        // pair-per-lane variant restores full bus width for 2-byte
-        // elements (u16 path: 2.3 TB/s; fp32: 4.2). Its u32 accesses
-        // are aligned only for 4-byte-aligned bases and even element
-        // offsets; any odd stride/extent/base takes the u16 kernel.
-        const long rows = shape[2], cols = shape[3];
-        const bool pair_aligned =
-            (((uintptr_t)src | (uintptr_t)dst) & 3) == 0 &&
-            ((strides[3] | strides[0] | strides[1] | cols) & 1) == 0;
-        if (!pair_aligned)
-          return ca_transpose_tiled_launch<uint16_t>(src, dst, shape,
-                                                     strides, stream);
-        dim3 grid((uint32_t)((rows + CA_TILE - 1) / CA_TILE),
-                  (uint32_t)((cols + CA_TILE - 1) / CA_TILE),
-                  (uint32_t)(shape[0] * shape[1]));
-        hipLaunchKernelGGL(transpose_tiled_pair16_kernel, grid, dim3(256),
-                           0, stream, (const uint16_t*)src, (uint16_t*)dst,
-                           rows, cols, strides[3], strides[0], strides[1],
-                           shape[1]);
-        return hipGetLastError();
-      }
-      case 4:
-        return ca_transpose_tiled_launch<uint32_t>(src, dst, shape, strides,
-                                                   stream);
-      case 8:
-        return ca_transpose_tiled_launch<uint64_t>(src, dst, shape, strides,
-                                                   stream);
-      default:
-        break;  // fall through to the scalar path
-    }
-  }
-  int grid = ca_grid_for(n);
-  const char* sp = (const char*)src;
-  switch (elem_size) {
-    case 1:
-      hipLaunchKernelGGL((gather_pack_kernel<uint8_t>), dim3(grid), dim3(256),
-                         0, stream, sp, (uint8_t*)dst, n, strides[0],
-                         strides[1], strides[2], strides[3], shape[0],
-                         shape[1], shape[2], shape[3]);
-      break;
-    case 2:
-      hipLaunchKernelGGL((gather_pack_kernel<uint16_t>), dim3(grid), dim3(256),
-                         0, stream, sp, (uint16_t*)dst, n, strides[0],
-                         strides[1], strides[2], strides[3], shape[0],
-                         shape[1], shape[2], shape[3]);
-      break;
-    case 4:
-      hipLaunchKernelGGL((gather_pack_kernel<uint32_t>), dim3(grid), dim3(256),
-                         0, stream, sp, (uint32_t*)dst, n, strides[0],
-                         strides[1], strides[2], strides[3], shape[0],
-                         shape[1], shape[2], shape[3]);
-      break;
-    case 8:
-      hipLaunchKernelGGL((gather_pack_kernel<uint64_t>), dim3(grid), dim3(256),
-                         0, stream, sp, (uint64_t*)dst, n, strides[0],
-                         strides[1], strides[2], strides[3], shape[0],
-                         shape[1], shape[2], shape[3]);
-      break;
-    default:
-      return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-extern "C" hipError_t ca_image_preprocess(const void* src, void* dst, int ih,
-                                          int iw, int oh, int ow, int mode,
-                                          int out_bf16, const float* mean,
-                                          const float* stdev,
-                                          hipStream_t stream) {
-  hipLaunchKernelGGL(image_preprocess_kernel,
-                     dim3(ca_grid_for((long)oh * ow)), dim3(256), 0, stream,
-                     (const uint8_t*)src, (float*)dst, ih, iw, oh, ow, mode,
-                     out_bf16, mean[0], mean[1], mean[2], stdev[0], stdev[1],
-                     stdev[2]);
-  return hipGetLastError();
-}
-
-// Batched variant: N same-sized images in one launch (u8 HWC stacked
-// contiguously -> NCHW). The single-image kernel is launch-bound at
-// high request rates (~27 us/image vs ~2-3 us of kernel time for
-// 224x224 — profiles/kernels_rocprof_r01.txt:19); the batch amortizes
-// one launch over the whole request. blockIdx.y = image index (grid.y
-// caps at 65535 — far above any sane batch).
-extern "C" __global__ void image_preprocess_batched_kernel(
-    const uint8_t* __restrict__ src, float* __restrict__ dst, int ih, int iw,
-    int oh, int ow, int mode, int out_bf16, float m0, float m1, float m2,
-    float s0, float s1, float s2) {
-  const long in_img = (long)ih * iw * 3;
-  const long n = (long)oh * ow;
-  const uint8_t* simg = src + (long)blockIdx.y * in_img;
-  float* dimg = dst + (long)blockIdx.y * 3 * n;
-  uint16_t* dimg16 =
-      reinterpret_cast<uint16_t*>(dst) + (long)blockIdx.y * 3 * n;
-  long i = (long)(blockIdx.x * blockDim.x + threadIdx.x);
-  const long stride = (long)gridDim.x * blockDim.x;
-  const float scale_h = (float)ih / oh;
-  const float scale_w = (float)iw / ow;
-  for (; i < n; i += stride) {
-    int oy = i / ow;
-    int ox = i % ow;
-    float fy = (oy + 0.5f) * scale_h - 0.5f;
-    float fx = (ox + 0.5f) * scale_w - 0.5f;
-    int y0 = max(0, (int)floorf(fy));
-    int x0 = max(0, (int)floorf(fx));
-    int y1 = min(ih - 1, y0 + 1);
-    int x1 = min(iw - 1, x0 + 1);
-    y0 = min(y0, ih - 1);
-    x0 = min(x0, iw - 1);
-    float wy = fy - floorf(fy);
-    float wx = fx - floorf(fx);
-    if (fy < 0) wy = 0.f;
-    if (fx < 0) wx = 0.f;
-    const uint8_t* p00 = simg + ((long)y0 * iw + x0) * 3;
-    const uint8_t* p01 = simg + ((long)y0 * iw + x1) * 3;
-    const uint8_t* p10 = simg + ((long)y1 * iw + x0) * 3;
-    const uint8_t* p11 = simg + ((long)y1 * iw + x1) * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      float v = (1 - wy) * ((1 - wx) * p00[c] + wx * p01[c]) +
-                wy * ((1 - wx) * p10[c] + wx * p11[c]);
-      float mean = c == 0 ? m0 : (c == 1 ? m1 : m2);
-      float sc = c == 0 ? s0 : (c == 1 ? s1 : s2);
-      if (mode == 1) {
-        v = v / 127.5f - 1.0f;
-      } else if (mode == 2) {
-        v = v - mean;
-      } else {
-        v = (v - mean) * sc;
-      }
-      long out_idx = (long)c * n + i;  // CHW within the image
-      if (out_bf16) {
-        dimg16[out_idx] = (uint16_t)(__float_as_uint(v) >> 16);
-      } else {
-        dimg[out_idx] = v;
-      }
-    }
-  }
-}
-
-extern "C" hipError_t ca_image_preprocess_batched(
-    const void* src, void* dst, int n_images, int ih, int iw, int oh, int ow,
-    int mode, int out_bf16, const float* mean, const float* stdev,
-    hipStream_t stream) {
-  if (n_images < 1 || n_images > 65535) return hipErrorInvalidValue;
-  dim3 grid((uint32_t)ca_grid_for((long)oh * ow), (uint32_t)n_images);
-  hipLaunchKernelGGL(image_preprocess_batched_kernel, grid, dim3(256), 0,
-                     stream, (const uint8_t*)src, (float*)dst, ih, iw, oh,
-                     ow, mode, out_bf16, mean[0], mean[1], mean[2], stdev[0],
-                     stdev[1], stdev[2]);
-  return hipGetLastError();
-}
-
-// Per-channel bias add over an NCHW bf16 tensor, in-place capable —
+// Per-plane NCHW epilogue, in-place capable. Without the residual it
 // absorbs the separate elementwise bias pass torch-on-ROCm emits for
 // conv biases created by BatchNorm folding (55 ms / 5247 calls in the
-// ResNet50 serving profile). One block per (n,c) plane: the fp32 bias
-// loads once, elements stream 8-wide with a scalar tail so any plane
-// size (incl. 7x7=49) is handled. Optional fused ReLU.
+// ResNet50 serving profile). With it, it is the bottleneck-exit fusion
+// (out = relu(x + bias[c] + residual)): after BN folding, torch-on-ROCm
+// runs this as three elementwise kernels (bias add, residual add,
+// relu), i.e. 3 extra full memory passes over the activation per block
+// exit; this kernel is one read-x + read-residual + write pass. fp32
+// math, RNE back to bf16.
+//
+// One block per (n,c) plane: the fp32 bias loads once, elements stream
+// 8-wide. There is no scalar tail: the launcher sends only planes with
+// ca_epilogue_per_plane(plane), i.e. plane % 8 == 0, here; every other
+// plane size (incl. 7x7=49) takes the flat kernels.
+template <bool HAS_RES>
+__device__ __forceinline__ void bias_res_act_plane_body(
+    const uint16_t* __restrict__ x, const uint16_t* __restrict__ res,
+    const float* __restrict__ bias, uint16_t* __restrict__ out, long plane,
+    int channels, int do_relu) {
+  const long pidx = blockIdx.x;  // n*C + c
+  const int c = (int)(pidx % channels);
+  const float b = bias[c];
+  const long vec_n = plane / 8;
+  const uint4* xv = (const uint4*)(x + pidx * plane);
+  const uint4* rv = HAS_RES ? (const uint4*)(res + pidx * plane) : nullptr;
+  uint4* ov = (uint4*)(out + pidx * plane);
+  for (long i = threadIdx.x; i < vec_n; i += blockDim.x) {
+    uint4 v = xv[i];
+    uint4 r = uint4{0, 0, 0, 0};
+    if (HAS_RES) r = rv[i];
+    uint32_t* w = (uint32_t*)&v;
+    const uint32_t* rw = (const uint32_t*)&r;
+    for (int j = 0; j < 4; ++j)
+      w[j] = epilogue_pair(w[j], rw[j], HAS_RES, b, b, do_relu);
+    ov[i] = v;
+  }
+}
+
 extern "C" __global__ void bias_act_bf16_kernel(
     const uint16_t* __restrict__ x, const float* __restrict__ bias,
     uint16_t* __restrict__ out, long plane, int channels, int do_relu) {
-  const long pidx = blockIdx.x;            // n*C + c
-  const int c = (int)(pidx % channels);
-  const float b = bias[c];
-  const uint16_t* xp = x + pidx * plane;
-  uint16_t* op = out + pidx * plane;
-  const long vec_n = plane / 8;
+  bias_res_act_plane_body<false>(x, nullptr, bias, out, plane, channels,
+                                 do_relu);
+}
 
-  auto apply = [&](uint16_t v) -> uint16_t {
-    float f = __uint_as_float(((uint32_t)v) << 16) + b;
-    if (do_relu && f < 0.f) f = 0.f;
-    // round-to-nearest-even bf16 (matches torch float->bf16 casts)
-    uint32_t u = __float_as_uint(f);
-    u += 0x7FFF + ((u >> 16) & 1);
-    return (uint16_t)(u >> 16);
-  };
-
-  const uint4* xv = (const uint4*)xp;
-  uint4* ov = (uint4*)op;
-  for (long i = threadIdx.x; i < vec_n; i += blockDim.x) {
-    uint4 v = xv[i];
-    uint32_t* w = (uint32_t*)&v;
-    for (int j = 0; j < 4; ++j) {
-      uint16_t lo = apply((uint16_t)(w[j] & 0xFFFF));
-      uint16_t hi = apply((uint16_t)(w[j] >> 16));
-      w[j] = (uint32_t)lo | ((uint32_t)hi << 16);
-    }
-    ov[i] = v;
-  }
-  for (long i = vec_n * 8 + threadIdx.x; i < plane; i += blockDim.x) {
-    op[i] = apply(xp[i]);
-  }
+extern "C" __global__ void bias_res_act_bf16_kernel(
+    const uint16_t* __restrict__ x, const uint16_t* __restrict__ res,
+    const float* __restrict__ bias, uint16_t* __restrict__ out, long plane,
+    int channels, int do_relu) {
+  bias_res_act_plane_body<true>(x, res, bias, out, plane, channels, do_relu);
 }
 
 // Flat-indexed NCHW epilogue: the same per-element math as the
@@ -1016,13 +987,6 @@ __device__ __forceinline__ void bias_res_act_flat_body(
     const uint16_t* __restrict__ x, const uint16_t* __restrict__ res,
     const float* __restrict__ bias, uint16_t* __restrict__ out, long total,
     long plane, int channels, long step_off, int step_c, int do_relu) {
-  auto fin = [&](float f) -> uint16_t {
-    if (do_relu && f < 0.f) f = 0.f;
-    uint32_t u = __float_as_uint(f);
-    u += 0x7FFF + ((u >> 16) & 1);  // RNE to bf16
-    return (uint16_t)(u >> 16);
-  };
-
   const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t e0 = tid * 8u;  // grid <= 2048 blocks: e0 < 2^22
   // plane <= e0 implies plane < 2^22, so the 32-bit division is exact
@@ -1066,18 +1030,9 @@ __device__ __forceinline__ void bias_res_act_flat_body(
     uint32_t* w = (uint32_t*)&v;
     const uint32_t* rw = (const uint32_t*)&r;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      // (x + residual) + bias: same order as the per-plane kernel and
-      // the torch reference (fp32 add is non-associative)
-      float lo = __uint_as_float((w[j] & 0xFFFFu) << 16);
-      float hi = __uint_as_float(w[j] & 0xFFFF0000u);
-      if (HAS_RES) {
-        lo += __uint_as_float((rw[j] & 0xFFFFu) << 16);
-        hi += __uint_as_float(rw[j] & 0xFFFF0000u);
-      }
-      w[j] = (uint32_t)fin(lo + bv[2 * j]) |
-             ((uint32_t)fin(hi + bv[2 * j + 1]) << 16);
-    }
+    for (int j = 0; j < 4; ++j)
+      w[j] = epilogue_pair(w[j], rw[j], HAS_RES, bv[2 * j], bv[2 * j + 1],
+                           do_relu);
     *reinterpret_cast<uint4*>(out + e) = v;
 
     off += step_off;
@@ -1092,9 +1047,8 @@ __device__ __forceinline__ void bias_res_act_flat_body(
   // ragged end: at most 7 elements, first lanes of block 0
   const long ti = (total / 8) * 8 + tid;
   if (tid < 8 && ti < total) {
-    float f = __uint_as_float(((uint32_t)x[ti]) << 16);
-    if (HAS_RES) f += __uint_as_float(((uint32_t)res[ti]) << 16);
-    out[ti] = fin(f + bias[(ti / plane) % channels]);
+    out[ti] = epilogue_one(x, HAS_RES ? res : nullptr, ti,
+                           bias[(ti / plane) % channels], do_relu);
   }
 }
 
@@ -1158,78 +1112,41 @@ hipError_t ca_launch_flat_epilogue(const void* x, const void* res,
 
 }  // namespace
 
+// residual may be null (degenerates to bias[+relu])
+extern "C" hipError_t ca_bias_res_act_bf16(const void* x, const void* res,
+                                           const void* bias, void* out,
+                                           long n_planes, long plane,
+                                           int channels, int do_relu,
+                                           hipStream_t stream) {
+  if (((uintptr_t)x & 15) || ((uintptr_t)out & 15) ||
+      ((uintptr_t)res & 15)) {
+    return hipErrorInvalidValue;  // 16B alignment for the uint4 path
+  }
+  if (!ca_epilogue_per_plane(plane)) {
+    return ca_launch_flat_epilogue(x, res, bias, out, n_planes, plane,
+                                   channels, do_relu, stream);
+  }
+  if (n_planes <= 0) return n_planes ? hipErrorInvalidValue : hipSuccess;
+  if (res) {
+    hipLaunchKernelGGL(bias_res_act_bf16_kernel, dim3((uint32_t)n_planes),
+                       dim3(256), 0, stream, (const uint16_t*)x,
+                       (const uint16_t*)res, (const float*)bias,
+                       (uint16_t*)out, plane, channels, do_relu);
+  } else {
+    hipLaunchKernelGGL(bias_act_bf16_kernel, dim3((uint32_t)n_planes),
+                       dim3(256), 0, stream, (const uint16_t*)x,
+                       (const float*)bias, (uint16_t*)out, plane, channels,
+                       do_relu);
+  }
+  return hipGetLastError();
+}
+
 extern "C" hipError_t ca_bias_act_bf16(const void* x, const void* bias,
                                        void* out, long n_planes, long plane,
                                        int channels, int do_relu,
                                        hipStream_t stream) {
-  if (((uintptr_t)x & 15) || ((uintptr_t)out & 15)) {
-    return hipErrorInvalidValue;  // 16B alignment for the uint4 path
-  }
-  if (!ca_epilogue_per_plane(plane)) {
-    return ca_launch_flat_epilogue(x, nullptr, bias, out, n_planes, plane,
-                                   channels, do_relu, stream);
-  }
-  if (n_planes <= 0) return n_planes ? hipErrorInvalidValue : hipSuccess;
-  hipLaunchKernelGGL(bias_act_bf16_kernel, dim3((uint32_t)n_planes),
-                     dim3(256), 0, stream, (const uint16_t*)x,
-                     (const float*)bias, (uint16_t*)out, plane, channels,
-                     do_relu);
-  return hipGetLastError();
-}
-
-// Per-channel bias + residual add + ReLU over NCHW bf16 in ONE pass —
-// the bottleneck-exit fusion (out = relu(x + bias[c] + residual)).
-// After BN folding, torch-on-ROCm runs this as three elementwise
-// kernels (bias add, residual add, relu), i.e. 3 extra full memory
-// passes over the activation per block exit; this kernel is one
-// read-x + read-residual + write pass. fp32 math, RNE back to bf16.
-// residual may be null (degenerates to bias[+relu]).
-extern "C" __global__ void bias_res_act_bf16_kernel(
-    const uint16_t* __restrict__ x, const uint16_t* __restrict__ res,
-    const float* __restrict__ bias, uint16_t* __restrict__ out, long plane,
-    int channels, int do_relu) {
-  const long pidx = blockIdx.x;  // n*C + c
-  const int c = (int)(pidx % channels);
-  const float b = bias[c];
-  const uint16_t* xp = x + pidx * plane;
-  const uint16_t* rp = res ? res + pidx * plane : nullptr;
-  uint16_t* op = out + pidx * plane;
-  const long vec_n = plane / 8;
-
-  auto fin = [&](float f) -> uint16_t {
-    if (do_relu && f < 0.f) f = 0.f;
-    uint32_t u = __float_as_uint(f);
-    u += 0x7FFF + ((u >> 16) & 1);  // RNE to bf16
-    return (uint16_t)(u >> 16);
-  };
-
-  const uint4* xv = (const uint4*)xp;
-  const uint4* rv = (const uint4*)rp;
-  uint4* ov = (uint4*)op;
-  for (long i = threadIdx.x; i < vec_n; i += blockDim.x) {
-    uint4 v = xv[i];
-    uint4 r = rp ? rv[i] : uint4{0, 0, 0, 0};
-    uint32_t* w = (uint32_t*)&v;
-    const uint32_t* rw = (const uint32_t*)&r;
-    for (int j = 0; j < 4; ++j) {
-      // addition order (x + residual) + bias matches the torch
-      // reference sequence exactly (fp32 add is non-associative;
-      // a different order flips RNE boundary cases)
-      float lo = __uint_as_float((w[j] & 0xFFFFu) << 16);
-      float hi = __uint_as_float(w[j] & 0xFFFF0000u);
-      if (rp) {
-        lo += __uint_as_float((rw[j] & 0xFFFFu) << 16);
-        hi += __uint_as_float(rw[j] & 0xFFFF0000u);
-      }
-      w[j] = (uint32_t)fin(lo + b) | ((uint32_t)fin(hi + b) << 16);
-    }
-    ov[i] = v;
-  }
-  for (long i = vec_n * 8 + threadIdx.x; i < plane; i += blockDim.x) {
-    float f = __uint_as_float(((uint32_t)xp[i]) << 16);
-    if (rp) f += __uint_as_float(((uint32_t)rp[i]) << 16);
-    op[i] = fin(f + b);
-  }
+  return ca_bias_res_act_bf16(x, nullptr, bias, out, n_planes, plane,
+                              channels, do_relu, stream);
 }
 
 // Channels-LAST (NHWC-contiguous) variant: channel is the fastest
@@ -1243,12 +1160,6 @@ extern "C" __global__ void bias_res_act_cl_bf16_kernel(
     const uint16_t* __restrict__ x, const uint16_t* __restrict__ res,
     const float* __restrict__ bias, uint16_t* __restrict__ out, long n,
     int channels, int do_relu) {
-  auto fin = [&](float f) -> uint16_t {
-    if (do_relu && f < 0.f) f = 0.f;
-    uint32_t u = __float_as_uint(f);
-    u += 0x7FFF + ((u >> 16) & 1);  // RNE to bf16
-    return (uint16_t)(u >> 16);
-  };
   long i0 = (long)(blockIdx.x * blockDim.x + threadIdx.x) * 8;
   long stride = (long)gridDim.x * blockDim.x * 8;
   for (long i = i0; i + 8 <= n; i += stride) {
@@ -1259,19 +1170,15 @@ extern "C" __global__ void bias_res_act_cl_bf16_kernel(
     const float4 b0 = *reinterpret_cast<const float4*>(bias + c0);
     const float4 b1 = *reinterpret_cast<const float4*>(bias + c0 + 4);
     const float bv[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-    uint32_t* w = (uint32_t*)&v;
+    const uint32_t* w = (const uint32_t*)&v;
     const uint32_t* rw = (const uint32_t*)&r;
     uint16_t o[8];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float lo = __uint_as_float((w[j] & 0xFFFFu) << 16);
-      float hi = __uint_as_float(w[j] & 0xFFFF0000u);
-      if (res) {
-        lo += __uint_as_float((rw[j] & 0xFFFFu) << 16);
-        hi += __uint_as_float(rw[j] & 0xFFFF0000u);
-      }
-      o[2 * j] = fin(lo + bv[2 * j]);
-      o[2 * j + 1] = fin(hi + bv[2 * j + 1]);
+      const uint32_t p = epilogue_pair(w[j], rw[j], res != nullptr, bv[2 * j],
+                                       bv[2 * j + 1], do_relu);
+      o[2 * j] = (uint16_t)p;
+      o[2 * j + 1] = (uint16_t)(p >> 16);
     }
     *reinterpret_cast<uint4*>(out + i) = *reinterpret_cast<uint4*>(o);
   }
@@ -1279,9 +1186,7 @@ extern "C" __global__ void bias_res_act_cl_bf16_kernel(
   long tail = (n / 8) * 8;
   long ti = tail + (blockIdx.x * blockDim.x + threadIdx.x);
   if (ti < n && (blockIdx.x * blockDim.x + threadIdx.x) < 8) {
-    float f = __uint_as_float(((uint32_t)x[ti]) << 16);
-    if (res) f += __uint_as_float(((uint32_t)res[ti]) << 16);
-    out[ti] = fin(f + bias[ti % channels]);
+    out[ti] = epilogue_one(x, res, ti, bias[ti % channels], do_relu);
   }
 }
 
@@ -1300,27 +1205,6 @@ extern "C" hipError_t ca_bias_res_act_cl_bf16(const void* x, const void* res,
                      (const uint16_t*)x, (const uint16_t*)res,
                      (const float*)bias, (uint16_t*)out, n, channels,
                      do_relu);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t ca_bias_res_act_bf16(const void* x, const void* res,
-                                           const void* bias, void* out,
-                                           long n_planes, long plane,
-                                           int channels, int do_relu,
-                                           hipStream_t stream) {
-  if (((uintptr_t)x & 15) || ((uintptr_t)out & 15) ||
-      ((uintptr_t)res & 15)) {
-    return hipErrorInvalidValue;  // 16B alignment for the uint4 path
-  }
-  if (!ca_epilogue_per_plane(plane)) {
-    return ca_launch_flat_epilogue(x, res, bias, out, n_planes, plane,
-                                   channels, do_relu, stream);
-  }
-  if (n_planes <= 0) return n_planes ? hipErrorInvalidValue : hipSuccess;
-  hipLaunchKernelGGL(bias_res_act_bf16_kernel, dim3((uint32_t)n_planes),
-                     dim3(256), 0, stream, (const uint16_t*)x,
-                     (const uint16_t*)res, (const float*)bias,
-                     (uint16_t*)out, plane, channels, do_relu);
   return hipGetLastError();
 }
 
@@ -1352,12 +1236,9 @@ __device__ __forceinline__ void bias_relu_maxpool_body(
   const uint32_t pl = row / (uint32_t)oh_n;  // n*C + c
   const float b = bias[pl % (uint32_t)channels];
 
+  // the epilogue's bf16 result, widened back to float for the max
   auto act = [&](uint16_t v) -> float {
-    float f = __uint_as_float(((uint32_t)v) << 16) + b;
-    if (f < 0.f) f = 0.f;
-    uint32_t u = __float_as_uint(f);
-    u += 0x7FFF + ((u >> 16) & 1);  // RNE to bf16
-    return __uint_as_float(u & 0xFFFF0000u);
+    return bf16_to_f32(epilogue_finish(bf16_to_f32(v) + b, 1));
   };
 
   const float ninf = __uint_as_float(0xFF800000u);
@@ -1397,6 +1278,7 @@ __device__ __forceinline__ void bias_relu_maxpool_body(
     }
   }
 
+  // m[] holds bf16 values, so truncation is exact
   uint16_t* op = out + ((size_t)pl * oh_n + oh) * ow_n + 4 * g;
   if (VEC) {
     uint2 o2;
@@ -1406,7 +1288,7 @@ __device__ __forceinline__ void bias_relu_maxpool_body(
   } else {
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
-      if (4 * (int)g + o < ow_n) op[o] = (uint16_t)(__float_as_uint(m[o]) >> 16);
+      if (4 * (int)g + o < ow_n) op[o] = f32_to_bf16_trunc(m[o]);
     }
   }
 }
@@ -1460,44 +1342,5 @@ extern "C" hipError_t ca_bias_relu_maxpool_bf16(const void* x,
                        (uint16_t*)out, (uint32_t)total, channels, h, w, oh_n,
                        ow_n, groups);
   }
-  return hipGetLastError();
-}
-
-extern "C" hipError_t ca_rmsnorm_bf16(const void* x, const void* w, void* out,
-                                      long rows, int dim, float eps,
-                                      hipStream_t stream) {
-  if (dim % 8 != 0) return hipErrorInvalidValue;
-  if (rows == 0) return hipSuccess;  // nothing to do; a zero grid is invalid
-  hipLaunchKernelGGL(rmsnorm_bf16_kernel, dim3((uint32_t)rows), dim3(256), 0,
-                     stream, (const uint16_t*)x, (const uint16_t*)w,
-                     (uint16_t*)out, dim, eps);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t ca_rope_decode_bf16(void* q, void* k,
-                                          const void* cos_tab,
-                                          const void* sin_tab,
-                                          const void* pos, int b, int hq,
-                                          int hk, int d, hipStream_t stream) {
-  long total = (long)b * (hq + hk) * (d / 2);
-  hipLaunchKernelGGL(rope_decode_bf16_kernel, dim3(ca_grid_for(total)),
-                     dim3(256), 0, stream, (uint16_t*)q, (uint16_t*)k,
-                     (const float*)cos_tab, (const float*)sin_tab,
-                     (const long*)pos, b, hq, hk, d);
-  return hipGetLastError();
-}
-
-extern "C" hipError_t ca_rope_scatter_decode_bf16(
-    void* q, const void* k, const void* v, void* ck, void* cv,
-    const void* cos_tab, const void* sin_tab, const void* pos, int b,
-    int hq, int hk, int d, long cache_len, float q_scale,
-    hipStream_t stream) {
-  long total = (long)b * (hq + 2 * hk) * (d / 2);
-  hipLaunchKernelGGL(rope_scatter_decode_bf16_kernel,
-                     dim3(ca_grid_for(total)), dim3(256), 0, stream,
-                     (uint16_t*)q, (const uint16_t*)k, (const uint16_t*)v,
-                     (uint16_t*)ck, (uint16_t*)cv, (const float*)cos_tab,
-                     (const float*)sin_tab, (const long*)pos, b, hq, hk, d,
-                     cache_len, q_scale);
   return hipGetLastError();
 }

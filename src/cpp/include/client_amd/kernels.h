@@ -33,11 +33,47 @@ hipError_t ca_image_preprocess(const void* src, void* dst, int ih, int iw,
                                int oh, int ow, int mode, int out_bf16,
                                const float* mean, const float* stdev,
                                hipStream_t stream);
+// the same for n_images same-sized images stacked contiguously -> NCHW
+hipError_t ca_image_preprocess_batched(const void* src, void* dst,
+                                       int n_images, int ih, int iw, int oh,
+                                       int ow, int mode, int out_bf16,
+                                       const float* mean, const float* stdev,
+                                       hipStream_t stream);
+// NCHW bf16 conv epilogue, in place allowed: out = x + bias[c], optional ReLU
+hipError_t ca_bias_act_bf16(const void* x, const void* bias, void* out,
+                            long n_planes, long plane, int channels,
+                            int do_relu, hipStream_t stream);
+// ... with a residual: out = (x + res) + bias[c], optional ReLU (res may be null)
+hipError_t ca_bias_res_act_bf16(const void* x, const void* res,
+                                const void* bias, void* out, long n_planes,
+                                long plane, int channels, int do_relu,
+                                hipStream_t stream);
+// ... over a channels-last (NHWC) tensor of n elements; channels % 8 == 0
+hipError_t ca_bias_res_act_cl_bf16(const void* x, const void* res,
+                                   const void* bias, void* out, long n,
+                                   int channels, int do_relu,
+                                   hipStream_t stream);
+// ResNet stem: bias + ReLU + 3x3 stride-2 pad-1 max-pool, NCHW bf16
+hipError_t ca_bias_relu_maxpool_bf16(const void* x, const void* bias,
+                                     void* out, long n_planes, int channels,
+                                     int h, int w, hipStream_t stream);
 // fused bf16 RMSNorm / per-row-position decode RoPE (LLM serving)
 hipError_t ca_rmsnorm_bf16(const void* x, const void* w, void* out, long rows,
                            int dim, float eps, hipStream_t stream);
 hipError_t ca_rope_decode_bf16(void* q, void* k, const void* cos_tab,
                                const void* sin_tab, const void* pos, int b,
                                int hq, int hk, int d, hipStream_t stream);
+// decode RoPE that also scatters rotated k and v into the KV cache
+// [b, hk, cache_len, d]; q is scaled by q_scale
+hipError_t ca_rope_scatter_decode_bf16(void* q, const void* k, const void* v,
+                                       void* ck, void* cv,
+                                       const void* cos_tab,
+                                       const void* sin_tab, const void* pos,
+                                       int b, int hq, int hk, int d,
+                                       long cache_len, float q_scale,
+                                       hipStream_t stream);
+// skinny decode GEMM y[8, N] = x[8, K] @ W[N, K]^T, bf16; K % 512 == 0
+hipError_t ca_decode_gemm_bf16(const void* x, const void* w, void* y, int N,
+                               int K, hipStream_t stream);
 
 }  // extern "C"

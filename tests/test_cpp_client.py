@@ -364,6 +364,21 @@ def test_cc_grpc_hipshm_example_gpu():
         server.wait(timeout=10)
 
 
+def test_kernels_header_matches_definitions(tmp_path):
+    """kernels.h and kernels.hip are never built together otherwise, so
+    compile them in one translation unit: a declaration that disagrees
+    with its extern "C" definition is a compile error."""
+    tu = tmp_path / "kernels_header_check.hip"
+    tu.write_text('#include "client_amd/kernels.h"\n'
+                  '#include "kernels.hip"\n')
+    proc = subprocess.run(
+        ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17",
+         "-fsyntax-only", f"-I{CPP}/include",
+         f"-I{REPO / 'client_amd' / 'ops' / 'csrc'}", str(tu)],
+        capture_output=True, text=True)
+    assert proc.returncode == 0, proc.stderr
+
+
 def test_cc_image_clients_compile():
     """image_client / ensemble_image_client need a GPU-backed resnet50
     to run; on CPU we verify they build and link."""
