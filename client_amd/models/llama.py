@@ -1,4 +1,4 @@
-"""Llama-3-8B-class decoder with KV cache and greedy generation
+"""Llama-3-8B-class decoder with KV cache, greedy and sampled generation
 (from scratch on torch.nn).
 
 BASELINE.md config 5: decoupled token streaming over gRPC — one
@@ -469,17 +469,29 @@ class LlamaModel(nn.Module):
         return self.lm_head(x_last)
 
     @torch.inference_mode()
-    def generate(self, input_ids, max_new_tokens):
-        """Greedy decode; yields one token id tensor [b] per step."""
+    def generate(self, input_ids, max_new_tokens, sampling=None):
+        """Yields one token id tensor [b] per step. Greedy unless
+        ``sampling``, a SamplingParams applied to every row, is given;
+        see client_amd.models.sampling. The first token is step 0."""
         device = next(self.parameters()).device
         dtype = next(self.parameters()).dtype
         input_ids = input_ids.to(device)
         b, s = input_ids.shape
+        if sampling is not None:
+            from .sampling import param_tensors, sample_tokens
+
+            temp, top_k, top_p, seed, step = param_tensors(
+                [sampling.validate().with_seed()] * b, [0] * b, device)
         kv_cache = self.make_kv_cache(b, device, dtype)
         logits = self.forward_step(input_ids, 0, kv_cache)
         pos = s
         for _ in range(max_new_tokens):
-            next_tok = logits.argmax(-1)
+            if sampling is None:
+                next_tok = logits.argmax(-1)
+            else:
+                next_tok = sample_tokens(logits.contiguous(), temp, top_k,
+                                         top_p, seed, step)
+                step += 1
             yield next_tok
             logits = self.forward_step(next_tok[:, None], pos, kv_cache)
             pos += 1

@@ -19,7 +19,7 @@
 //   - bias_act_bf16 / bias_res_act_bf16 / bias_res_act_cl_bf16 /
 //     bias_relu_maxpool_bf16 (ResNet50 conv epilogues, NCHW and NHWC)
 //   - rmsnorm_bf16 / rope_decode_bf16 / rope_scatter_decode_bf16 /
-//     decode_gemm_bf16 (LLM decode step)
+//     decode_gemm_bf16 / sample_logits_bf16 (LLM decode step)
 //
 // The cast, pack and preprocess kernels are memory-bound streaming
 // kernels: 16 B/lane vectorized access, 256-thread blocks (4 waves of
@@ -409,6 +409,17 @@ static void image_preprocess_batched(uintptr_t src, uintptr_t dst,
   sync_if(sync, s);
 }
 
+static void sample_logits_bf16(uintptr_t logits, uintptr_t temperature,
+                               uintptr_t top_k, uintptr_t top_p,
+                               uintptr_t seed, uintptr_t step, uintptr_t out,
+                               long rows, int vocab,
+                               uintptr_t stream_handle) {
+  HIP_CHECK(ca_sample_logits_bf16(
+      cptr(logits), cptr(temperature), cptr(top_k), cptr(top_p), cptr(seed),
+      cptr(step), mptr(out), rows, vocab,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
 PYBIND11_MODULE(_hip_c, m) {
   m.doc() = "client_amd MI355X HIP runtime + CDNA4 kernels";
   m.def("device_count", &device_count);
@@ -468,6 +479,10 @@ PYBIND11_MODULE(_hip_c, m) {
   m.def("rmsnorm_bf16", &rmsnorm_bf16, py::arg("x"), py::arg("w"),
         py::arg("out"), py::arg("rows"), py::arg("dim"), py::arg("eps"),
         py::arg("stream_handle"));
+  m.def("sample_logits_bf16", &sample_logits_bf16, py::arg("logits"),
+        py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
+        py::arg("seed"), py::arg("step"), py::arg("out"), py::arg("rows"),
+        py::arg("vocab"), py::arg("stream_handle"));
   m.def("rope_decode_bf16", &rope_decode_bf16, py::arg("q"), py::arg("k"),
         py::arg("cos_tab"), py::arg("sin_tab"), py::arg("pos"), py::arg("b"),
         py::arg("hq"), py::arg("hk"), py::arg("d"),

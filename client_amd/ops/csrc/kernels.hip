@@ -873,6 +873,464 @@ extern "C" hipError_t ca_decode_gemm_bf16(const void* x, const void* w,
   return hipGetLastError();
 }
 
+// Token sampling from bf16 logits: temperature, top-k, top-p and a
+// per-row counter-based random draw, one workgroup per row, placed
+// where argmax sits in the decode step. Every per-row parameter is read
+// from device memory, so a captured launch sees new values on replay.
+//
+// Contract per row (tests/sampling_refs.py is the float64 statement):
+//   - logits are sanitised: NaN reads as -inf, +inf as the largest
+//     finite bf16, -0 as +0; a row with no finite logit yields token 0
+//   - temperature 0 (also negative or NaN, which callers reject) yields
+//     the lowest index holding the maximum
+//   - K = logits >= the k-th largest (ties included); weights
+//     w = exp((l - l_max) / T); N = logits >= the largest distinct value
+//     whose tail mass reaches top_p * S_K (ties included)
+//   - u = (x0 >> 8) * 2^-24, x0 = word 0 of Philox4x32-10 with counter
+//     (step, 0, 0) and key seed; the token is the first index of N, in
+//     index order, whose running weight exceeds u * S_N
+//
+// bf16 maps monotonically onto a 16-bit key, so both thresholds are
+// two-level 256-bin radix selections in LDS (counts for top-k, weight
+// sums for top-p) and nothing is sorted. A weight depends on the key
+// alone and is held as a 2^-44 fixed-point integer: every sum is an
+// exact, order-independent integer sum, which makes the token a pure
+// function of (row contents, parameters, seed, step) whatever the row
+// index, batch or replay. The first pass reads the row from HBM, later
+// passes hit L2. Each wave owns a contiguous chunk of the row, so the
+// per-wave totals of the last pass locate the draw and only that wave
+// walks its chunk again with a running scan. Rows may start on any
+// 2-byte boundary: a scalar head and tail surround the 16 B/lane body.
+#define SL_THREADS 1024
+#define SL_WAVES (SL_THREADS / 64)
+#define SL_COPIES 16         // histogram replicas: same-bin lanes spread
+#define SL_KEY_NEG_INF 0x007Fu
+#define SL_ONE (1ull << 44)  // fixed-point 1.0
+
+namespace {
+
+typedef unsigned long long sl_u64;
+
+// sanitised bf16 bits -> key with the same order as the values; never 0,
+// so 0 marks an absent element
+__device__ __forceinline__ uint32_t sl_key(uint32_t x) {
+  if ((x & 0x7FFFu) > 0x7F80u) x = 0xFF80u;  // NaN -> -inf
+  else if (x == 0x7F80u) x = 0x7F7Fu;        // +inf -> largest finite
+  else if (x == 0x8000u) x = 0u;             // -0 -> +0
+  return (x & 0x8000u) ? (~x & 0xFFFFu) : (x | 0x8000u);
+}
+
+__device__ __forceinline__ float sl_key_value(uint32_t key) {
+  const uint32_t h = (key & 0x8000u) ? (key & 0x7FFFu) : (~key & 0xFFFFu);
+  return __uint_as_float(h << 16);
+}
+
+// A row as nvec 8-element vectors in index order: vector 0 is the
+// scalar head (up to the first 16 B boundary), 1..nbody the aligned
+// body, nbody+1 the scalar tail. Head and tail may be empty.
+struct SlRow {
+  const uint16_t* p;
+  int vocab, head, nbody, nvec;
+};
+
+__device__ __forceinline__ SlRow sl_row(const uint16_t* logits, long row,
+                                        int vocab) {
+  SlRow r;
+  r.p = logits + row * vocab;
+  r.vocab = vocab;
+  const int head = (int)(((16u - ((uintptr_t)r.p & 15u)) & 15u) >> 1);
+  r.head = head < vocab ? head : vocab;
+  r.nbody = (vocab - r.head) >> 3;
+  r.nvec = r.nbody + 2;
+  return r;
+}
+
+// Vector v of a row as loaded: raw bf16 pairs, index of the first
+// element, number of elements present (0 for v outside the row)
+struct SlVec {
+  uint4 q;
+  int e0, cnt;
+};
+
+__device__ __forceinline__ SlVec sl_load(const SlRow& r, int v, int end) {
+  SlVec x;
+  x.q = make_uint4(0u, 0u, 0u, 0u);
+  x.e0 = 0;
+  x.cnt = 0;
+  if (v >= end) return x;
+  if (v >= 1 && v <= r.nbody) {
+    x.e0 = r.head + ((v - 1) << 3);
+    x.cnt = 8;
+    x.q = *reinterpret_cast<const uint4*>(r.p + x.e0);
+    return x;
+  }
+  x.e0 = v == 0 ? 0 : r.head + (r.nbody << 3);
+  x.cnt = v == 0 ? r.head : r.vocab - x.e0;
+  uint32_t h[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) h[j] = j < x.cnt ? r.p[x.e0 + j] : 0u;
+  x.q = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16),
+                   h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+  return x;
+}
+
+// keys of a loaded vector, 0 where the element does not exist
+__device__ __forceinline__ void sl_keys(const SlVec& x, uint32_t k[8]) {
+  const uint32_t w[4] = {x.q.x, x.q.y, x.q.z, x.q.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    k[2 * j] = 2 * j < x.cnt ? sl_key(w[j] & 0xFFFFu) : 0u;
+    k[2 * j + 1] = 2 * j + 1 < x.cnt ? sl_key(w[j] >> 16) : 0u;
+  }
+}
+
+// Each wave owns a contiguous chunk of the row's vectors, [lo, hi), and
+// walks it 64 vectors (1 KiB) at a time.
+__device__ __forceinline__ void sl_chunk(const SlRow& r, int& lo, int& hi) {
+  const int per = (r.nvec + SL_WAVES - 1) / SL_WAVES;
+  lo = (int)(threadIdx.x >> 6) * per;
+  hi = lo + per < r.nvec ? lo + per : r.nvec;
+}
+
+// f(keys, e0) over this thread's share of the row, in no particular
+// order. Four loads are in flight per thread: with one workgroup per row
+// a pass is bound by load latency, not by bandwidth.
+template <typename F>
+__device__ __forceinline__ void sl_for_each(const SlRow& r, F f) {
+  int lo, hi;
+  sl_chunk(r, lo, hi);
+  for (int v = lo + (int)(threadIdx.x & 63); v < hi; v += 256) {
+    SlVec x[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) x[u] = sl_load(r, v + 64 * u, hi);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      uint32_t k[8];
+      sl_keys(x[u], k);
+      f(k, x[u].e0);
+    }
+  }
+}
+
+// fixed-point weight of a key, 2^((l - l_max) * scale) with scale =
+// log2(e) / T; the maximum is exactly 1 so a temperature too small to
+// invert still leaves the maximum its mass
+__device__ __forceinline__ sl_u64 sl_weight(uint32_t key, uint32_t maxkey,
+                                            float lmax, float scale) {
+  if (key == maxkey) return SL_ONE;
+  const float w = exp2f((sl_key_value(key) - lmax) * scale);
+  return w > 0.f ? (sl_u64)(w * 0x1p44f) : 0ull;
+}
+
+// block-wide max / sum, result in every thread; scratch holds SL_WAVES
+__device__ __forceinline__ sl_u64 sl_block_max(sl_u64 v, sl_u64* scratch) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const sl_u64 t = __shfl_xor(v, off);
+    v = t > v ? t : v;
+  }
+  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
+  __syncthreads();
+  sl_u64 m = scratch[0];
+#pragma unroll
+  for (int i = 1; i < SL_WAVES; ++i) m = scratch[i] > m ? scratch[i] : m;
+  __syncthreads();
+  return m;
+}
+
+__device__ __forceinline__ sl_u64 sl_block_sum(sl_u64 v, sl_u64* scratch) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
+  __syncthreads();
+  sl_u64 s = 0;
+#pragma unroll
+  for (int i = 0; i < SL_WAVES; ++i) s += scratch[i];
+  __syncthreads();
+  return s;
+}
+
+// inclusive scan over the 64 lanes of a wave
+__device__ __forceinline__ sl_u64 sl_wave_scan(sl_u64 v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const sl_u64 t = __shfl_up(v, off);
+    if (lane >= off) v += t;
+  }
+  return v;
+}
+
+// One histogram pass over the row: f(key, bin, val) says whether the key
+// takes part and with what; returns this thread's sum of val. Ends with
+// the histogram complete and visible.
+template <typename F>
+__device__ __forceinline__ sl_u64 sl_hist_pass(const SlRow& r, sl_u64* hist,
+                                               F f) {
+  for (int i = threadIdx.x; i < 256 * SL_COPIES; i += SL_THREADS) hist[i] = 0;
+  __syncthreads();
+  const int copy = threadIdx.x & (SL_COPIES - 1);
+  sl_u64 local = 0;
+  sl_for_each(r, [&](const uint32_t k[8], int) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      int bin = 0;
+      sl_u64 val = 0;
+      if (k[j] != 0u && f(k[j], bin, val) && val != 0ull) {
+        atomicAdd(&hist[bin * SL_COPIES + copy], val);
+        local += val;
+      }
+    }
+  });
+  __syncthreads();
+  return local;
+}
+
+struct SlSel {
+  int bin;       // highest bin whose tail sum (itself included) >= need
+  sl_u64 above;  // sum of the bins above it
+  sl_u64 incl;   // above + the bin itself
+};
+
+// Radix-select step on a complete histogram: bin = -1 when even the sum
+// of all bins stays below need. need >= 1. Called by every thread.
+__device__ __forceinline__ SlSel sl_select(const sl_u64* hist, sl_u64 need,
+                                           sl_u64* scratch, SlSel* sh) {
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  sl_u64 mine = 0;  // thread t < 256 owns bin 255 - t: scan order = top down
+  if (tid < 256) {
+    const sl_u64* h = hist + (255 - tid) * SL_COPIES;
+#pragma unroll
+    for (int c = 0; c < SL_COPIES; ++c) mine += h[c];
+  }
+  sl_u64 incl = sl_wave_scan(mine);
+  if (tid == 0) sh->bin = -1;
+  if ((tid & 63) == 63 && wave < 4) scratch[wave] = incl;
+  __syncthreads();
+  if (tid < 256) {
+    for (int i = 0; i < wave; ++i) incl += scratch[i];
+    if (incl >= need && incl - mine < need) {
+      sh->bin = 255 - tid;
+      sh->above = incl - mine;
+      sh->incl = incl;
+    }
+  }
+  __syncthreads();
+  return *sh;
+}
+
+__device__ __forceinline__ uint32_t sl_philox_word0(sl_u64 seed, sl_u64 ctr) {
+  uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0u, c3 = 0u;
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return c0;
+}
+
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(SL_THREADS)
+sample_logits_bf16_kernel(const uint16_t* __restrict__ logits,
+                          const float* __restrict__ temperature,
+                          const int* __restrict__ top_k,
+                          const float* __restrict__ top_p,
+                          const sl_u64* __restrict__ seed,
+                          const long* __restrict__ step,
+                          long* __restrict__ out, int vocab) {
+  __shared__ sl_u64 hist[256 * SL_COPIES];  // 32 KB
+  __shared__ sl_u64 scratch[SL_WAVES];
+  __shared__ SlSel sh_sel;
+  __shared__ int sh_found;
+  const int tid = threadIdx.x;
+  const int row = blockIdx.x;
+  const SlRow r = sl_row(logits, row, vocab);
+  const float temp = temperature[row];
+  const int k = top_k[row];
+  const float p = top_p[row];
+  const bool sampled = temp > 0.f;  // NaN compares false
+  const bool use_k = sampled && k > 0 && k < vocab;
+  const bool use_p = sampled && p < 1.f;
+  const int copy = tid & (SL_COPIES - 1);
+
+  // pass 1 (HBM): maximum and its lowest index, packed so one max finds
+  // both; with top-k on, also the level-1 count histogram
+  if (use_k) {
+    for (int i = tid; i < 256 * SL_COPIES; i += SL_THREADS) hist[i] = 0;
+    __syncthreads();
+  }
+  sl_u64 best = 0;
+  sl_for_each(r, [&](const uint32_t key[8], int e0) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (key[j] == 0u) continue;
+      const sl_u64 cand =
+          ((sl_u64)key[j] << 32) | (sl_u64)(0xFFFFFFFFu - (uint32_t)(e0 + j));
+      best = cand > best ? cand : best;
+      if (use_k) atomicAdd(&hist[(key[j] >> 8) * SL_COPIES + copy], 1ull);
+    }
+  });
+  best = sl_block_max(best, scratch);
+  const uint32_t maxkey = (uint32_t)(best >> 32);
+  const long argmax = (long)(0xFFFFFFFFu - (uint32_t)best);
+  if (!sampled || maxkey <= SL_KEY_NEG_INF) {
+    if (tid == 0) out[row] = maxkey <= SL_KEY_NEG_INF ? 0 : argmax;
+    return;
+  }
+
+  // top-k: kk = key of the k-th largest, K = {key >= kk}
+  uint32_t kk = 0u;
+  if (use_k) {
+    const SlSel s1 = sl_select(hist, (sl_u64)k, scratch, &sh_sel);
+    if (s1.bin >= 0) {
+      const uint32_t b1 = (uint32_t)s1.bin;
+      sl_hist_pass(r, hist, [b1](uint32_t key, int& bin, sl_u64& val) {
+        bin = (int)(key & 255u);
+        val = 1ull;
+        return (key >> 8) == b1;
+      });
+      const SlSel s2 =
+          sl_select(hist, (sl_u64)k - s1.above, scratch, &sh_sel);
+      if (s2.bin >= 0) kk = (b1 << 8) | (uint32_t)s2.bin;
+    }
+  }
+
+  // top-p over the weights of K: nk = key of the last distinct value
+  // kept, N = {key >= nk}
+  const float lmax = sl_key_value(maxkey);
+  const float scale = (1.0f / temp) * 1.44269504088896341f;
+  uint32_t nk = kk;
+  if (use_p) {
+    const sl_u64 s_k = sl_block_sum(
+        sl_hist_pass(r, hist,
+                     [=](uint32_t key, int& bin, sl_u64& val) {
+                       if (key < kk) return false;
+                       bin = (int)(key >> 8);
+                       val = sl_weight(key, maxkey, lmax, scale);
+                       return true;
+                     }),
+        scratch);
+    // smallest integer mass m with m >= top_p * s_k
+    const double thr = ceil((double)p * (double)s_k);
+    sl_u64 need = thr > 1.0 ? (sl_u64)thr : 1ull;
+    if (need > s_k) need = s_k;
+    const SlSel s1 = sl_select(hist, need, scratch, &sh_sel);
+    if (s1.bin >= 0) {
+      const uint32_t b1 = (uint32_t)s1.bin;
+      sl_hist_pass(r, hist, [=](uint32_t key, int& bin, sl_u64& val) {
+        if (key < kk || (key >> 8) != b1) return false;
+        bin = (int)(key & 255u);
+        val = sl_weight(key, maxkey, lmax, scale);
+        return true;
+      });
+      const SlSel s2 = sl_select(hist, need - s1.above, scratch, &sh_sel);
+      if (s2.bin >= 0) nk = (b1 << 8) | (uint32_t)s2.bin;
+    }
+  }
+
+  // the weight of N per wave chunk; their sum is s_n. Chunks are in
+  // index order, so the wave whose chunk holds the draw is known from
+  // the totals alone.
+  sl_u64 mine = 0;
+  int last = -1;  // highest index of N this thread saw
+  sl_for_each(r, [&](const uint32_t key[8], int e0) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (key[j] != 0u && key[j] >= nk) {
+        mine += sl_weight(key[j], maxkey, lmax, scale);
+        last = e0 + j > last ? e0 + j : last;
+      }
+    }
+  });
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+  if ((tid & 63) == 0) scratch[tid >> 6] = mine;
+  if (tid == 0) sh_found = -1;
+  __syncthreads();
+  sl_u64 s_n = 0, before = 0;  // before: weight of the chunks in front
+#pragma unroll
+  for (int i = 0; i < SL_WAVES; ++i) {
+    if (i < (tid >> 6)) before += scratch[i];
+    s_n += scratch[i];
+  }
+
+  // the draw: first index of N whose running weight exceeds u * s_n,
+  // i.e. exceeds floor(m * s_n / 2^24) with u = m * 2^-24
+  const sl_u64 m = (sl_u64)(sl_philox_word0(seed[row], (sl_u64)step[row]) >> 8);
+  const sl_u64 target = (__umul64hi(m, s_n) << 40) | ((m * s_n) >> 24);
+  if (mine != 0ull && before <= target && target < before + mine) {
+    // this wave's chunk holds it: walk the chunk in order, one wave scan
+    // per 64 vectors, the next load issued before the current is used
+    int lo, hi;
+    sl_chunk(r, lo, hi);
+    sl_u64 running = before;
+    int v = lo + (tid & 63);
+    SlVec cur = sl_load(r, v, hi);
+    for (; v - (tid & 63) < hi; v += 64) {
+      const SlVec nxt = sl_load(r, v + 64, hi);
+      uint32_t key[8];
+      sl_u64 w[8];
+      sl_keys(cur, key);
+      sl_u64 sum = 0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        w[j] = (key[j] != 0u && key[j] >= nk)
+                   ? sl_weight(key[j], maxkey, lmax, scale)
+                   : 0ull;
+        sum += w[j];
+      }
+      const sl_u64 incl = sl_wave_scan(sum);
+      sl_u64 cum = running + incl - sum;  // weight before this lane
+      const bool here = sum != 0ull && cum <= target && target < cum + sum;
+      if (here) {
+        int found = -1;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          cum += w[j];
+          if (found < 0 && w[j] != 0ull && cum > target) found = cur.e0 + j;
+        }
+        sh_found = found;
+      }
+      if (__any(here)) break;
+      running += __shfl(incl, 63);
+      cur = nxt;
+    }
+  }
+  __syncthreads();
+  int found = sh_found;
+  if (found < 0) {
+    // no running sum passed the target (only if every weight is zero):
+    // the last index of N
+    const sl_u64 l = sl_block_max((sl_u64)(last + 1), scratch);
+    found = l > 0 ? (int)(l - 1) : (int)argmax;
+  }
+  if (tid == 0) out[row] = found;
+}
+
+extern "C" hipError_t ca_sample_logits_bf16(
+    const void* logits, const void* temperature, const void* top_k,
+    const void* top_p, const void* seed, const void* step, void* out,
+    long rows, int vocab, hipStream_t stream) {
+  if (rows < 0 || rows > 0x7FFFFFFFl || vocab < 1) return hipErrorInvalidValue;
+  if ((uintptr_t)logits & 1) return hipErrorInvalidValue;
+  if (rows == 0) return hipSuccess;  // nothing to do; a zero grid is invalid
+  hipLaunchKernelGGL(sample_logits_bf16_kernel, dim3((uint32_t)rows),
+                     dim3(SL_THREADS), 0, stream, (const uint16_t*)logits,
+                     (const float*)temperature, (const int*)top_k,
+                     (const float*)top_p, (const sl_u64*)seed,
+                     (const long*)step, (long*)out, vocab);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // ResNet epilogues: per-channel bias (+ residual) (+ ReLU) over bf16
 // ---------------------------------------------------------------------------

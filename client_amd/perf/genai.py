@@ -9,6 +9,12 @@ token throughput.
 
     python -m client_amd.perf.genai -m llama3_8b -u 127.0.0.1:8001 \
         --concurrency 4 --prompt-tokens 128 --output-tokens 64 --requests 8
+
+Sampling parameters go to the model as extra inputs, in the reference
+genai tool's ``--extra-inputs NAME:VALUE`` style:
+
+        --extra-inputs temperature:0.8 --extra-inputs top_k:50 \
+        --extra-inputs top_p:0.9 --extra-inputs seed:1
 """
 
 import argparse
@@ -41,10 +47,38 @@ def _stats_ms(sorted_vals, scale=1000.0, digits=3):
     }
 
 
+# extra inputs a GenerateModel accepts: name -> (datatype, numpy dtype,
+# parser)
+EXTRA_INPUT_TYPES = {
+    "temperature": ("FP32", np.float32, float),
+    "top_k": ("INT32", np.int32, int),
+    "top_p": ("FP32", np.float32, float),
+    "seed": ("UINT64", np.uint64, int),
+}
+
+
+def parse_extra_inputs(items):
+    """['temperature:0.8', 'seed:7'] -> {'temperature': 0.8, 'seed': 7},
+    typed by name; unknown names and malformed values raise ValueError."""
+    out = {}
+    for item in items or []:
+        name, sep, value = item.partition(":")
+        if not sep or name not in EXTRA_INPUT_TYPES:
+            raise ValueError(
+                f"--extra-inputs expects NAME:VALUE with NAME one of "
+                f"{sorted(EXTRA_INPUT_TYPES)}, got '{item}'")
+        try:
+            out[name] = EXTRA_INPUT_TYPES[name][2](value)
+        except ValueError:
+            raise ValueError(
+                f"--extra-inputs {name}: cannot parse '{value}'") from None
+    return out
+
+
 class GenAiPerf:
     def __init__(self, url, model_name, prompt_tokens=128, output_tokens=64,
                  vocab_size=128256, verbose=False, warmup_requests=0,
-                 seed=None):
+                 seed=None, extra_inputs=None):
         self.url = url
         self.model_name = model_name
         self.prompt_tokens = prompt_tokens
@@ -55,6 +89,11 @@ class GenAiPerf:
         # --warmup-request-count)
         self.warmup_requests = warmup_requests
         self.seed = seed
+        # sent with every request (sampling parameters)
+        self.extra_inputs = dict(extra_inputs or {})
+        for name in self.extra_inputs:
+            if name not in EXTRA_INPUT_TYPES:
+                raise ValueError(f"unknown extra input '{name}'")
 
     def _one_stream_worker(self, n_requests, out):
         import client_amd.grpc as grpcclient
@@ -78,6 +117,11 @@ class GenAiPerf:
                 inputs[0].set_data_from_numpy(ids)
                 inputs[1].set_data_from_numpy(
                     np.array([self.output_tokens], dtype=np.int32))
+                for name, value in self.extra_inputs.items():
+                    datatype, npdt, _ = EXTRA_INPUT_TYPES[name]
+                    extra = grpcclient.InferInput(name, [1], datatype)
+                    extra.set_data_from_numpy(np.array([value], dtype=npdt))
+                    inputs.append(extra)
                 t0 = time.monotonic()
                 client.async_stream_infer(
                     self.model_name, inputs,
@@ -131,6 +175,7 @@ class GenAiPerf:
             "warmup_requests_per_stream": self.warmup_requests,
             "prompt_tokens": self.prompt_tokens,
             "output_tokens_per_request": self.output_tokens,
+            "extra_inputs": dict(self.extra_inputs),
             "total_output_tokens": total_tokens,
             "output_tokens_per_sec": round(total_tokens / elapsed, 2),
             "request_throughput_per_sec": round(n_req / elapsed, 3),
@@ -155,14 +200,23 @@ def main(argv=None):
     p.add_argument("--warmup-request-count", type=int, default=0,
                    help="per-stream unmeasured warmup requests")
     p.add_argument("--random-seed", type=int, default=None)
+    p.add_argument("--extra-inputs", action="append", default=[],
+                   metavar="NAME:VALUE",
+                   help="extra input sent with every request; repeatable "
+                        "(temperature, top_k, top_p, seed)")
     p.add_argument("--json", default=None)
     args = p.parse_args(argv)
+    try:
+        extra_inputs = parse_extra_inputs(args.extra_inputs)
+    except ValueError as e:
+        p.error(str(e))
 
     ga = GenAiPerf(
         url=args.url, model_name=args.model_name,
         prompt_tokens=args.prompt_tokens, output_tokens=args.output_tokens,
         vocab_size=args.vocab_size,
         warmup_requests=args.warmup_request_count, seed=args.random_seed,
+        extra_inputs=extra_inputs,
     )
     result = ga.run(concurrency=args.concurrency,
                     requests_per_stream=args.requests)

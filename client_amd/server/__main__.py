@@ -13,7 +13,7 @@ import threading
 
 
 def build_core(model_names, device="cuda:0", dtype="bf16",
-               decode_max_batch=8):
+               decode_max_batch=8, prewarm_sampling=False):
     from . import (
         AddSubModel,
         IdentityModel,
@@ -121,7 +121,8 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
             core.add_model(
                 GenerateModel(name, module, device=device,
                               dtype=tdt if use_gpu else None,
-                              max_batch=decode_max_batch)
+                              max_batch=decode_max_batch,
+                              prewarm_sampling=prewarm_sampling)
             )
         elif name == "ensemble_image":
             # preprocess (HIP kernel on GPU) -> resnet50 pipeline; the
@@ -190,6 +191,11 @@ def main(argv=None):
     parser.add_argument("--max-queue-delay-us", type=int, default=500)
     parser.add_argument("--decode-max-batch", type=int, default=8,
                         help="continuous-batching slots for generate models")
+    parser.add_argument("--prewarm-sampling", action="store_true",
+                        help="also capture the sampled variants of the "
+                             "decode and prefill hipGraphs at start-up "
+                             "(otherwise captured on the first sampled "
+                             "request)")
     parser.add_argument("--model-warmup", action="store_true",
                         help="pre-capture hipGraphs / prime MIOpen for the "
                              "serving batch sizes before READY is printed")
@@ -198,6 +204,7 @@ def main(argv=None):
     core = build_core(
         [m for m in args.models.split(",") if m], args.device, args.dtype,
         decode_max_batch=args.decode_max_batch,
+        prewarm_sampling=args.prewarm_sampling,
     )
     if args.dynamic_batching:
         for model in core.models.values():

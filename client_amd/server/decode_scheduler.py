@@ -19,10 +19,12 @@ import threading
 
 import torch
 
+from ..models.sampling import sample_tokens, seed_to_i64
+
 
 class _Slot:
     __slots__ = ("state", "pos", "last_token", "remaining", "out_queue",
-                 "prefill_ids", "prefill_pos")
+                 "prefill_ids", "prefill_pos", "sampling", "step")
     FREE, PREFILL, ACTIVE = 0, 1, 2
 
     def __init__(self):
@@ -33,6 +35,10 @@ class _Slot:
         self.out_queue = None
         self.prefill_ids = None
         self.prefill_pos = 0
+        # SamplingParams with its seed set, or None for greedy; step
+        # counts the request's tokens (the prefill token is step 0)
+        self.sampling = None
+        self.step = 0
 
     @property
     def active(self):
@@ -72,7 +78,9 @@ class DecodeScheduler:
         self._scratch = model.scratch_pos
         self._pos_dev = torch.full((max_batch,), self._scratch,
                                    dtype=torch.int64, device=device)
-        self._graphs = {}  # bucket -> (graph, next_tokens_out)
+        # bucket -> (graph, next_tokens_out); the sampled variant of a
+        # bucket is a separate entry under (bucket, True)
+        self._graphs = {}
         # batched prefill: one static-shape forward advances the
         # mid-prefill slots by one chunk (replacing the per-slot eager
         # loop whose 32-layer launch overhead stalled decode ~86 ms per
@@ -82,7 +90,9 @@ class DecodeScheduler:
         # shape measured as a 60+ ms replay (8x512 positions of GEMM)
         # and made the stall WORSE.
         self._pf_bufs = {}    # group_size -> dict of persistent tensors
-        self._pf_graphs = {}  # (group_size, bucket) -> (graph, out)
+        # (group_size, bucket) -> (graph, out); sampled variants under
+        # (group_size, bucket, True)
+        self._pf_graphs = {}
         # cap prefill rows advanced per loop iteration: a start burst
         # admitting max_batch prompts at once would otherwise run one
         # [8, C] replay (~45 ms measured) in a single decode gap;
@@ -102,29 +112,36 @@ class DecodeScheduler:
         busy = sum(1 for s in self.slots if s.state != _Slot.FREE)
         return busy / max(1, len(self.slots))
 
-    def prewarm(self, n_buckets=2):
+    def prewarm(self, n_buckets=2, sampling=False):
         """Capture the first n decode-graph buckets up front. A cold
         capture costs ~0.5 s and otherwise lands in the first stream's
         TTFT (measured: TTFT p90 590 ms cold vs ~50 ms warm) — the
-        MI355X analog of the reference's ModelWarmup."""
+        MI355X analog of the reference's ModelWarmup. ``sampling`` also
+        captures the sampled variant of every one of them (off by
+        default: it doubles the captures, and start-up time with it)."""
         if not self.use_graph:
             return
+        self._prewarm(n_buckets, False)
+        if sampling:
+            self._prewarm(n_buckets, True)
+
+    def _prewarm(self, n_buckets, sampled):
         for i in range(1, n_buckets + 1):
             bucket = min(i * self.len_bucket, self.model.cfg.max_seq)
-            self._get_graph(bucket)
+            self._get_graph(bucket, sampled)
             # capture every group size the scheduler can actually issue
             # (1..prefill_rows_per_step, powers of two) — an uncaptured
             # (group, bucket) pair costs ~0.5 s in some stream's TTFT
             g = 1
             while g <= max(1, self.prefill_rows_per_step):
-                self._get_prefill_graph(g, bucket)
+                self._get_prefill_graph(g, bucket, sampled)
                 g *= 2
             if i <= 2:
                 # idle-burst shape: with nothing decoding the cap lifts
                 # to max_batch, so the first bursts replay (max_batch,
                 # low-bucket) graphs
                 self._get_prefill_graph(self._group_size(self.max_batch),
-                                        bucket)
+                                        bucket, sampled)
             if bucket >= self.model.cfg.max_seq:
                 break
 
@@ -133,11 +150,19 @@ class DecodeScheduler:
             self._alive = False
             self._cv.notify()
 
-    def submit(self, input_ids, max_new_tokens):
-        """Returns a queue yielding token ids (ints), then END."""
+    def submit(self, input_ids, max_new_tokens, sampling=None):
+        """Returns a queue yielding token ids (ints), then END.
+
+        ``sampling`` is a client_amd.models.sampling.SamplingParams;
+        None or temperature 0 decodes greedily. Invalid parameters
+        raise ValueError here, before the request is queued. A missing
+        seed is replaced by a random 64-bit one."""
+        if sampling is not None:
+            sampling = (None if sampling.validate().is_greedy
+                        else sampling.with_seed())
         out = queue.Queue()
         with self._cv:
-            self._pending.put((input_ids, max_new_tokens, out))
+            self._pending.put((input_ids, max_new_tokens, out, sampling))
             self._cv.notify()
         return out
 
@@ -152,7 +177,8 @@ class DecodeScheduler:
             if not free:
                 return
             try:
-                input_ids, max_new, out = self._pending.get_nowait()
+                (input_ids, max_new, out,
+                 sampling) = self._pending.get_nowait()
             except queue.Empty:
                 return
             idx = free[0]
@@ -168,6 +194,8 @@ class DecodeScheduler:
             slot.prefill_pos = 0
             slot.remaining = max_new
             slot.out_queue = out
+            slot.sampling = sampling
+            slot.step = 0
 
     def _pf_buffers(self, group):
         bufs = self._pf_bufs.get(group)
@@ -226,17 +254,51 @@ class DecodeScheduler:
                     pass
         return None
 
-    def _get_prefill_graph(self, group, bucket):
-        entry = self._pf_graphs.get((group, bucket))
+    def _pf_sampling(self, group):
+        """Persistent per-row sampling parameters of a prefill group
+        (temperature, top_k, top_p, seed, step), allocated on the first
+        sampled request that needs them."""
+        bufs = self._pf_buffers(group)
+        if "sampling" not in bufs:
+            bufs["sampling"] = self._sampling_tensors(group, self.device,
+                                                      pin=False)
+        return bufs["sampling"]
+
+    @staticmethod
+    def _sampling_tensors(rows, device, pin):
+        return (
+            torch.zeros(rows, dtype=torch.float32, device=device,
+                        pin_memory=pin),
+            torch.zeros(rows, dtype=torch.int32, device=device,
+                        pin_memory=pin),
+            torch.ones(rows, dtype=torch.float32, device=device,
+                       pin_memory=pin),
+            torch.zeros(rows, dtype=torch.int64, device=device,
+                        pin_memory=pin),
+            torch.zeros(rows, dtype=torch.int64, device=device,
+                        pin_memory=pin),
+        )
+
+    def _get_prefill_graph(self, group, bucket, sampled=False):
+        key = (group, bucket, True) if sampled else (group, bucket)
+        entry = self._pf_graphs.get(key)
         if entry is not None:
             return entry
         bufs = self._pf_buffers(group)
         args = (bufs["tokens"], bufs["pos"], bufs["lens"], bufs["last"],
                 self.kv_cache, bucket, bufs["rows"])
-        entry = self._capture_graph(
-            lambda: self.model.forward_prefill_chunk(*args).argmax(-1)
-        ) or self._EAGER
-        self._pf_graphs[(group, bucket)] = entry
+        if sampled:
+            params = self._pf_sampling(group)
+            entry = self._capture_graph(
+                lambda: sample_tokens(
+                    self.model.forward_prefill_chunk(*args).contiguous(),
+                    *params)
+            ) or self._EAGER
+        else:
+            entry = self._capture_graph(
+                lambda: self.model.forward_prefill_chunk(*args).argmax(-1)
+            ) or self._EAGER
+        self._pf_graphs[key] = entry
         return entry
 
     @staticmethod
@@ -297,9 +359,24 @@ class DecodeScheduler:
                 max_end = max(max_end, end)
             bucket = self._bucket(max_end)
             bufs = self._pf_buffers(group)
+            # the sampled variant only when a row of this group samples;
+            # its rows' first token is step 0, greedy rows carry
+            # temperature 0
+            sampled = any(self.slots[i].sampling is not None
+                          for i in group_slots)
+            if sampled:
+                params = self._pf_sampling(group)
+                host = self._sampling_tensors(group, "cpu", pin=False)
+                for g, i in enumerate(group_slots):
+                    sp = self.slots[i].sampling
+                    if sp is not None:
+                        host[0][g] = sp.temperature
+                        host[1][g] = sp.top_k
+                        host[2][g] = sp.top_p
+                        host[3][g] = seed_to_i64(sp.seed)
             # resolve (or capture) the graph BEFORE taking the shared
             # execution guard — capture takes the exclusive side
-            entry = (self._get_prefill_graph(group, bucket)
+            entry = (self._get_prefill_graph(group, bucket, sampled)
                      if self.use_graph else self._EAGER)
             from .models import GRAPH_EXEC_SHARED
 
@@ -309,6 +386,9 @@ class DecodeScheduler:
                 bufs["lens"].copy_(lens)
                 bufs["last"].copy_(last)
                 bufs["rows"].copy_(rows)
+                if sampled:
+                    for dst, src in zip(params, host):
+                        dst.copy_(src)
                 if entry is not self._EAGER:
                     graph, first_out = entry
                     graph.replay()
@@ -320,7 +400,11 @@ class DecodeScheduler:
                             bufs["last"], self.kv_cache, bucket,
                             bufs["rows"],
                         )
-                        firsts = logits.argmax(-1).tolist()
+                        if sampled:
+                            firsts = sample_tokens(logits.contiguous(),
+                                                   *params).tolist()
+                        else:
+                            firsts = logits.argmax(-1).tolist()
             for g, i in enumerate(group_slots):
                 slot = self.slots[i]
                 end, total = ends[i]
@@ -332,6 +416,7 @@ class DecodeScheduler:
                 slot.prefill_ids = None
                 slot.pos = total  # position the NEXT token writes at
                 slot.last_token = first
+                slot.step = 1
                 slot.remaining -= 1
                 if slot.remaining <= 0:
                     slot.state = _Slot.FREE
@@ -373,7 +458,82 @@ class DecodeScheduler:
             self._out_np = out.numpy()
         return out
 
-    def _get_graph(self, bucket):
+    def _sampling_staging(self):
+        """(host, device) per-row sampling parameters of the decode
+        batch — temperature, top_k, top_p, seed, step — staged like
+        th/ph: reused pinned host tensors, persistent device tensors.
+        Allocated on the first sampled request; on a CPU scheduler the
+        host tensors are the device tensors."""
+        st = getattr(self, "_samp", None)
+        if st is None:
+            if str(self.device).startswith("cuda"):
+                host = self._sampling_tensors(self.max_batch, "cpu",
+                                              pin=True)
+                dev = self._sampling_tensors(self.max_batch, self.device,
+                                             pin=False)
+            else:
+                host = dev = self._sampling_tensors(self.max_batch, "cpu",
+                                                    pin=False)
+            st = (host, dev, tuple(t.numpy() for t in host))
+            self._samp = st
+        return st
+
+    def _stage_sampling(self):
+        """Fill the host staging from the slots: rows that are greedy
+        or not decoding carry temperature 0."""
+        _, _, (temp, top_k, top_p, seed, step) = self._sampling_staging()
+        for i, s in enumerate(self.slots):
+            sp = s.sampling if s.active else None
+            if sp is None:
+                temp[i] = 0.0
+                continue
+            temp[i] = sp.temperature
+            top_k[i] = sp.top_k
+            top_p[i] = sp.top_p
+            seed[i] = seed_to_i64(sp.seed)
+            step[i] = s.step
+
+    def _copy_sampling(self):
+        host, dev, _ = self._sampling_staging()
+        if host is not dev:
+            for d, h in zip(dev, host):
+                d.copy_(h, non_blocking=True)
+
+    def _get_sampled_graph(self, bucket):
+        """Sampled variant of the decode graph: the same step with
+        sample_tokens where argmax sits, reading the persistent
+        parameter tensors (in wide mode their H2D copies are graph
+        nodes too)."""
+        entry = self._graphs.get((bucket, True))
+        if entry is not None:
+            return entry
+        _, params, _ = self._sampling_staging()
+        wide = self._wide_graph
+        if wide:
+            th, ph, _, _ = self._host_staging()
+            out_pinned = self._wide_out()
+
+        def fwd():
+            if wide:
+                self._tokens_dev.copy_(th, non_blocking=True)
+                self._pos_dev.copy_(ph, non_blocking=True)
+                self._copy_sampling()
+            out = sample_tokens(
+                self.model.forward_decode_batch(
+                    self._tokens_dev, self._pos_dev, self.kv_cache,
+                    max_len=bucket,
+                ).contiguous(), *params)
+            if wide:
+                out_pinned.copy_(out, non_blocking=True)
+            return out
+
+        entry = self._capture_graph(fwd) or self._EAGER
+        self._graphs[(bucket, True)] = entry
+        return entry
+
+    def _get_graph(self, bucket, sampled=False):
+        if sampled:
+            return self._get_sampled_graph(bucket)
         entry = self._graphs.get(bucket)
         if entry is not None:
             return entry
@@ -431,6 +591,11 @@ class DecodeScheduler:
         for i, s in enumerate(self.slots):
             tnp[i] = s.last_token
             pnp[i] = max(s.pos, 1) if s.active else self._scratch
+        # the sampled variant of the step only while a decoding row
+        # samples; otherwise nothing below differs from greedy decode
+        sampled = any(self.slots[i].sampling is not None for i in active)
+        if sampled:
+            self._stage_sampling()
         if self.use_graph:
             trace2 = getattr(self, "_trace2", None)
             if trace2 is None:
@@ -448,7 +613,7 @@ class DecodeScheduler:
             max_pos = max(s.pos for s in self.slots if s.active)
             # graph resolution (possible capture = exclusive) happens
             # BEFORE the shared execution guard
-            entry = self._get_graph(self._bucket(max_pos + 1))
+            entry = self._get_graph(self._bucket(max_pos + 1), sampled)
             from .models import GRAPH_EXEC_SHARED
 
             if trace2:
@@ -458,6 +623,8 @@ class DecodeScheduler:
                 if not wide:
                     self._tokens_dev.copy_(th, non_blocking=True)
                     self._pos_dev.copy_(ph, non_blocking=True)
+                    if sampled:
+                        self._copy_sampling()
                 if wide:
                     # everything (H2D, forward, argmax, D2H) is inside
                     # the graph; the pinned staging is already filled
@@ -482,7 +649,7 @@ class DecodeScheduler:
                         )
                     if trace2:
                         c = _t.monotonic_ns()
-                    next_tokens = logits.argmax(-1).tolist()
+                    next_tokens = self._pick(logits, sampled)
             if trace2:
                 d = _t.monotonic_ns()
                 acc = self._t2_acc
@@ -504,18 +671,30 @@ class DecodeScheduler:
                 logits = self.model.forward_decode_batch(
                     self._tokens_dev, self._pos_dev, self.kv_cache
                 )
-                next_tokens = logits.argmax(-1).tolist()
+                if sampled:
+                    self._copy_sampling()
+                next_tokens = self._pick(logits, sampled)
         for i in active:
             slot = self.slots[i]
             tok = int(next_tokens[i])
             slot.out_queue.put(tok)
             slot.last_token = tok
+            slot.step += 1
             slot.pos += 1
             slot.remaining -= 1
             if slot.remaining <= 0 or slot.pos >= self.model.cfg.max_seq - 1:
                 slot.state = _Slot.FREE
                 slot.out_queue.put(self.END)
         return True
+
+    def _pick(self, logits, sampled):
+        """Eager token choice: the same sample_tokens the sampled graphs
+        capture, or argmax."""
+        if not sampled:
+            return logits.argmax(-1).tolist()
+        with torch.inference_mode():
+            return sample_tokens(logits.contiguous(),
+                                 *self._sampling_staging()[1]).tolist()
 
     def _fail_all_streams(self, exc):
         """Recovery path for an unexpected error inside a scheduler
@@ -533,6 +712,7 @@ class DecodeScheduler:
             slot.state = _Slot.FREE
             slot.prefill_ids = None
             slot.out_queue = None
+            slot.sampling = None
         try:
             torch.cuda.synchronize()
         except Exception:

@@ -256,13 +256,20 @@ class GenerateModel(Model):
     """Decoupled LLM token streaming: one response per generated token
     (the decoupled protocol is the reference's
     repeat_int32 shape, simple_grpc_custom_repeat.cc:135-176, applied to
-    a real decode loop with KV cache)."""
+    a real decode loop with KV cache).
+
+    Optional per-request sampling inputs, each of shape [1]:
+    ``temperature`` FP32 (default 0 = greedy), ``top_k`` INT32 (0 = off),
+    ``top_p`` FP32 (1 = off) and ``seed`` UINT64 (random when absent).
+    A request without any of them decodes greedily."""
 
     def __init__(self, name, llama_module, device="cuda:0", dtype=None,
-                 use_scheduler=True, max_batch=8):
+                 use_scheduler=True, max_batch=8, prewarm_sampling=False):
         super().__init__(
             name,
-            [("input_ids", "INT64", [-1]), ("max_tokens", "INT32", [1])],
+            [("input_ids", "INT64", [-1]), ("max_tokens", "INT32", [1]),
+             ("temperature", "FP32", [1]), ("top_k", "INT32", [1]),
+             ("top_p", "FP32", [1]), ("seed", "UINT64", [1])],
             [("token_id", "INT64", [1]), ("index", "INT32", [1])],
             platform="pytorch",
             decoupled=True,
@@ -287,7 +294,8 @@ class GenerateModel(Model):
             # 4 buckets = up to 1024 total tokens hiccup-free (an
             # uncaptured bucket showed up as one 86 ms ITL outlier in
             # the 512-token soak).
-            self._scheduler.prewarm(n_buckets=4)
+            self._scheduler.prewarm(n_buckets=4,
+                                    sampling=prewarm_sampling)
 
     def load_metrics(self):
         """ORCA named metrics for the endpoint-load-metrics header."""
@@ -295,14 +303,50 @@ class GenerateModel(Model):
             return {}
         return {"kv_cache_utilization": self._scheduler.kv_utilization}
 
+    @staticmethod
+    def _sampling_from(inputs):
+        """SamplingParams from the optional inputs, or None when the
+        request carries none of them. An invalid value is an
+        InferenceError naming the input, raised before the request
+        reaches the scheduler."""
+        names = ("temperature", "top_k", "top_p", "seed")
+        if not any(n in inputs for n in names):
+            return None
+        from ..models.sampling import SamplingParams
+        from .core import InferenceError
+
+        def scalar(name, cast, default):
+            if name not in inputs:
+                return default
+            arr = np.asarray(inputs[name]).reshape(-1)
+            if arr.size != 1:
+                raise InferenceError(
+                    f"input '{name}' must hold exactly one element, "
+                    f"got {arr.size}")
+            return cast(arr[0])
+
+        params = SamplingParams(
+            temperature=scalar("temperature", float, 0.0),
+            top_k=scalar("top_k", int, 0),
+            top_p=scalar("top_p", float, 1.0),
+            seed=scalar("seed", int, None),
+        )
+        try:
+            params.validate()
+        except ValueError as e:
+            raise InferenceError(f"invalid value for input '"
+                                 f"{str(e).split(' ', 1)[0]}': {e}") from e
+        return params
+
     def execute_decoupled(self, inputs, parameters):
         torch = self._torch
         max_tokens = int(inputs.get("max_tokens", np.array([16]))[0])
+        sampling = self._sampling_from(inputs)
         if self._scheduler is not None:
             # continuous batching: concurrent streams share one decode
             # loop (see decode_scheduler.py)
             ids = np.ascontiguousarray(inputs["input_ids"].astype(np.int64))
-            out = self._scheduler.submit(ids, max_tokens)
+            out = self._scheduler.submit(ids, max_tokens, sampling)
             idx = 0
             while True:
                 tok = out.get(timeout=600)
@@ -317,7 +361,10 @@ class GenerateModel(Model):
         input_ids = torch.from_numpy(
             np.ascontiguousarray(inputs["input_ids"].astype(np.int64))
         )[None]
-        for idx, tok in enumerate(self.module.generate(input_ids, max_tokens)):
+        if sampling is not None and sampling.is_greedy:
+            sampling = None
+        for idx, tok in enumerate(
+                self.module.generate(input_ids, max_tokens, sampling)):
             yield {
                 "token_id": tok.detach().cpu().numpy().astype(np.int64),
                 "index": np.array([idx], dtype=np.int32),

@@ -75,5 +75,12 @@ hipError_t ca_rope_scatter_decode_bf16(void* q, const void* k, const void* v,
 // skinny decode GEMM y[8, N] = x[8, K] @ W[N, K]^T, bf16; K % 512 == 0
 hipError_t ca_decode_gemm_bf16(const void* x, const void* w, void* y, int N,
                                int K, hipStream_t stream);
+// token sampling from bf16 logits [rows, vocab]: per-row temperature (f32),
+// top_k (i32), top_p (f32), seed (u64) and step (i64) in device memory;
+// out [rows] int64
+hipError_t ca_sample_logits_bf16(const void* logits, const void* temperature,
+                                 const void* top_k, const void* top_p,
+                                 const void* seed, const void* step, void* out,
+                                 long rows, int vocab, hipStream_t stream);
 
 }  // extern "C"
