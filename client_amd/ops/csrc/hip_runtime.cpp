@@ -20,6 +20,10 @@
 //     bias_relu_maxpool_bf16 (ResNet50 conv epilogues, NCHW and NHWC)
 //   - rmsnorm_bf16 / rope_decode_bf16 / rope_scatter_decode_bf16 /
 //     decode_gemm_bf16 / sample_logits_bf16 (LLM decode step)
+//   - rope_scatter_decode_fp8kv_bf16 (the same scatter into an e4m3 KV
+//     cache) / gqa_decode_attention + gqa_decode_attention_workspace_bytes
+//     (fused split + combine decode attention over a bf16 or e4m3 cache;
+//     GQA_DECODE_SPLIT is its split size in keys)
 //
 // The cast, pack and preprocess kernels are memory-bound streaming
 // kernels: 16 B/lane vectorized access, 256-thread blocks (4 waves of
@@ -381,6 +385,33 @@ static void rope_scatter_decode_bf16(uintptr_t q, uintptr_t k, uintptr_t v,
       reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
+static void rope_scatter_decode_fp8kv_bf16(
+    uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t ck, uintptr_t cv,
+    uintptr_t cos_tab, uintptr_t sin_tab, uintptr_t pos, int b, int hq,
+    int hk, int d, long cache_len, float q_scale, uintptr_t stream_handle) {
+  HIP_CHECK(ca_rope_scatter_decode_fp8kv_bf16(
+      mptr(q), cptr(k), cptr(v), mptr(ck), mptr(cv), cptr(cos_tab),
+      cptr(sin_tab), cptr(pos), b, hq, hk, d, cache_len, q_scale,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
+static long gqa_decode_attention_workspace_bytes(int b, int hq, int d,
+                                                 long max_len) {
+  return ca_gqa_decode_attention_workspace_bytes(b, hq, d, max_len);
+}
+
+static void gqa_decode_attention(uintptr_t q, uintptr_t ck, uintptr_t cv,
+                                 uintptr_t pos, uintptr_t out,
+                                 uintptr_t workspace, long workspace_bytes,
+                                 int b, int hq, int hk, int d, float scale,
+                                 long max_len, long cache_len, bool kv_fp8,
+                                 uintptr_t stream_handle) {
+  HIP_CHECK(ca_gqa_decode_attention(
+      cptr(q), cptr(ck), cptr(cv), cptr(pos), mptr(out), mptr(workspace),
+      workspace_bytes, b, hq, hk, d, scale, max_len, cache_len,
+      kv_fp8 ? 1 : 0, reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
 static void image_preprocess(uintptr_t src, uintptr_t dst, int ih, int iw,
                              int oh, int ow, int mode, bool out_bf16,
                              std::vector<float> mean, std::vector<float> stdev,
@@ -492,6 +523,22 @@ PYBIND11_MODULE(_hip_c, m) {
         py::arg("cos_tab"), py::arg("sin_tab"), py::arg("pos"), py::arg("b"),
         py::arg("hq"), py::arg("hk"), py::arg("d"), py::arg("cache_len"),
         py::arg("q_scale") = 1.0f, py::arg("stream_handle") = 0);
+  m.def("rope_scatter_decode_fp8kv_bf16", &rope_scatter_decode_fp8kv_bf16,
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("ck"),
+        py::arg("cv"), py::arg("cos_tab"), py::arg("sin_tab"), py::arg("pos"),
+        py::arg("b"), py::arg("hq"), py::arg("hk"), py::arg("d"),
+        py::arg("cache_len"), py::arg("q_scale") = 1.0f,
+        py::arg("stream_handle") = 0);
+  m.attr("GQA_DECODE_SPLIT") = GA_SPLIT;
+  m.def("gqa_decode_attention_workspace_bytes",
+        &gqa_decode_attention_workspace_bytes, py::arg("b"), py::arg("hq"),
+        py::arg("d"), py::arg("max_len"));
+  m.def("gqa_decode_attention", &gqa_decode_attention, py::arg("q"),
+        py::arg("ck"), py::arg("cv"), py::arg("pos"), py::arg("out"),
+        py::arg("workspace"), py::arg("workspace_bytes"), py::arg("b"),
+        py::arg("hq"), py::arg("hk"), py::arg("d"), py::arg("scale"),
+        py::arg("max_len"), py::arg("cache_len"), py::arg("kv_fp8"),
+        py::arg("stream_handle"));
   m.def("gather_pack", &gather_pack, py::arg("src"), py::arg("dst"),
         py::arg("elem_size"), py::arg("shape"), py::arg("strides"),
         py::arg("device") = 0, py::arg("sync") = true);

@@ -774,6 +774,472 @@ extern "C" hipError_t ca_rope_scatter_decode_bf16(
   return hipGetLastError();
 }
 
+// The same step for an fp8 (OCP e4m3fn) KV cache: ck/cv hold one code
+// per element. q is rotated exactly as above; k is rotated and rounded
+// to bf16 by the same rope_rotate_pair, then encoded (CastF32ToFp8's
+// contract: RNE, finite values saturate to +-448), so the cache holds
+// the e4m3 encoding of what the bf16 cache would hold. A lane's two
+// adjacent codes go out as one 16-bit store. Rows whose position is
+// outside [0, cache_len) write nothing at all.
+extern "C" __global__ void rope_scatter_decode_fp8kv_bf16_kernel(
+    uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
+    const uint16_t* __restrict__ v, uint8_t* __restrict__ ck,
+    uint8_t* __restrict__ cv, const float* __restrict__ cos_tab,
+    const float* __restrict__ sin_tab, const long* __restrict__ pos, int b,
+    int hq, int hk, int d, long cache_len, float q_scale) {
+  const int half = d / 2;
+  const long total = (long)b * (hq + 2 * hk) * half;
+  long i = (long)(blockIdx.x * blockDim.x + threadIdx.x);
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (; i < total; i += stride) {
+    long rem = i;
+    const int j = (int)(rem % half);
+    rem /= half;
+    const int head = (int)(rem % (hq + 2 * hk));
+    const int row = (int)(rem / (hq + 2 * hk));
+    const long p = pos[row];
+    if (p < 0 || p >= cache_len) continue;
+    if (head < hq) {
+      uint16_t* base = q + ((long)row * hq + head) * d;
+      rope_rotate_pair(base, base, j, cos_tab[p * half + j],
+                       sin_tab[p * half + j], q_scale);
+      continue;
+    }
+    uint16_t pair[2];
+    uint8_t* dst;
+    if (head < hq + hk) {
+      const int h = head - hq;
+      rope_rotate_pair(k + ((long)row * hk + h) * d + 2 * j, pair, 0,
+                       cos_tab[p * half + j], sin_tab[p * half + j], 1.0f);
+      dst = ck + (((long)row * hk + h) * cache_len + p) * d;
+    } else {
+      const int h = head - hq - hk;
+      const uint16_t* base = v + ((long)row * hk + h) * d;
+      pair[0] = base[2 * j];
+      pair[1] = base[2 * j + 1];
+      dst = cv + (((long)row * hk + h) * cache_len + p) * d;
+    }
+    const uint32_t lo = CastF32ToFp8::convert(bf16_to_f32(pair[0]));
+    const uint32_t hi = CastF32ToFp8::convert(bf16_to_f32(pair[1]));
+    *reinterpret_cast<uint16_t*>(dst + 2 * j) = (uint16_t)(lo | (hi << 8));
+  }
+}
+
+extern "C" hipError_t ca_rope_scatter_decode_fp8kv_bf16(
+    void* q, const void* k, const void* v, void* ck, void* cv,
+    const void* cos_tab, const void* sin_tab, const void* pos, int b,
+    int hq, int hk, int d, long cache_len, float q_scale,
+    hipStream_t stream) {
+  // the packed 16-bit code stores need even addresses
+  if (d % 2 != 0 || ((uintptr_t)ck | (uintptr_t)cv) % 2 != 0)
+    return hipErrorInvalidValue;
+  long total = (long)b * (hq + 2 * hk) * (d / 2);
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL(rope_scatter_decode_fp8kv_bf16_kernel,
+                     dim3(ca_grid_for(total)), dim3(256), 0, stream,
+                     (uint16_t*)q, (const uint16_t*)k, (const uint16_t*)v,
+                     (uint8_t*)ck, (uint8_t*)cv, (const float*)cos_tab,
+                     (const float*)sin_tab, (const long*)pos, b, hq, hk, d,
+                     cache_len, q_scale);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Fused GQA decode attention (one query position per row, per-row
+// lengths): out[i, h] = softmax_j(scale * q[i, h] . K[i, g, j]) V[i, g, j]
+// over the keys j < n_i = min(pos[i] + 1, max_len) of kv head g = h / rep.
+//
+// Split kernel: grid (key split, kv head, row), GA_SPLIT keys per split.
+// One workgroup serves all rep query heads of its kv head, so K/V are
+// read once. A group of LPK lanes owns one key row and loads it 16 B per
+// lane; all of a lane's K loads, then all its V loads, are issued before
+// the first use. Scores go to LDS, wave r takes the exact fp32 softmax
+// of head r over the split's keys (max m, p = exp(s - m), sum l), and the
+// groups accumulate p * V in fp32, reduced across the groups of a wave
+// by shuffles and across the four waves through LDS in a fixed order.
+// The partial (m, l, acc[d]) of each (row, head, split) goes to an fp32
+// workspace. Keys at j >= n_i are never loaded, and a split with no key
+// writes nothing.
+//
+// Combine kernel: one workgroup per (row, head) merges the row's
+// ceil(n_i / GA_SPLIT) partials in ascending order, each rescaled by
+// exp(m_split - m_row), and rounds once (RNE) to bf16.
+//
+// No atomics and no arrival counters: the split a key falls in and every
+// reduction order depend on the key's index alone, so a row's output
+// bits do not depend on b, max_len, the row's index or its neighbours.
+//
+// The two kernels are templates on (storage type, head dim, padded rep)
+// launched directly, 36 instantiations, not one extern "C" entry point
+// each; their names in a trace carry the template arguments.
+// ---------------------------------------------------------------------------
+#define GA_SPLIT 128    // keys per split (exported to Python)
+#define GA_THREADS 256
+#define GA_WS_PAD 4     // floats ahead of acc[d] in a partial: m, l, 2 unused
+
+namespace {
+
+// 16 bytes of stored K/V -> fp32
+__device__ __forceinline__ void ga_unpack(const uint4& w, float (&f)[8],
+                                          const uint16_t*) {
+  const uint32_t u[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f[2 * i] = bf16x2_lo(u[i]);
+    f[2 * i + 1] = bf16x2_hi(u[i]);
+  }
+}
+__device__ __forceinline__ void ga_unpack(const uint4& w, float (&f)[16],
+                                          const uint8_t*) {
+  const uint32_t u[4] = {w.x, w.y, w.z, w.w};
+#if defined(__gfx950__)
+  // two codes per hardware convert
+  typedef float ga_f32x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const ga_f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)u[i], false);
+    const ga_f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)u[i], true);
+    f[4 * i] = lo[0];
+    f[4 * i + 1] = lo[1];
+    f[4 * i + 2] = hi[0];
+    f[4 * i + 3] = hi[1];
+  }
+#else
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    f[i] = CastFp8ToF32::convert((uint8_t)(u[i / 4] >> (8 * (i % 4))));
+#endif
+}
+
+template <typename T, int D, int REP>
+__device__ __forceinline__ void ga_split_body(
+    const uint16_t* __restrict__ q, const T* __restrict__ ck,
+    const T* __restrict__ cv, const long* __restrict__ pos,
+    float* __restrict__ ws, int hq, int hk, int rep, float scale,
+    long max_len, long cache_len, int n_splits) {
+  constexpr int VEC = 16 / (int)sizeof(T);  // elements per 16-byte load
+  constexpr int LPK = D / VEC;              // lanes per key row
+  constexpr int GROUPS = GA_THREADS / LPK;  // key rows in flight
+  constexpr int KPG = (GA_SPLIT + GROUPS - 1) / GROUPS;  // keys per group
+  static_assert(LPK >= 1 && LPK <= 16 && D % VEC == 0, "head dim");
+
+  __shared__ float s_p[REP][GA_SPLIT];   // scores, then probabilities
+  __shared__ float s_ml[REP][2];
+  __shared__ float s_acc[4][REP][D];     // per-wave accumulators
+
+  const int split = blockIdx.x;
+  const int g_kv = blockIdx.y;
+  const int row = blockIdx.z;
+  long n = pos[row] + 1;
+  if (n > max_len) n = max_len;
+  const long first = (long)split * GA_SPLIT;
+  if (first >= n) return;  // empty split (block-uniform)
+  const int cnt = (int)((n - first < GA_SPLIT) ? (n - first) : GA_SPLIT);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int grp = tid / LPK;
+  const int sub = tid % LPK;
+
+  const long kv_base = (((long)row * hk + g_kv) * cache_len + first) * D;
+  const T* kp = ck + kv_base + sub * VEC;
+  const T* vp = cv + kv_base + sub * VEC;
+
+  // loads return in issue order: q first, then K, then V, so the
+  // scores start while V is still in flight. All loads are unconditional
+  // (a branch around a load costs a wait at its join): a lane whose key
+  // is past the split's last one re-reads that last key, a padded head
+  // re-reads the last real head, and neither result is ever stored.
+  constexpr int QW = VEC / 8;  // 16-byte words of a lane's q slice
+  uint4 qbuf[REP][QW];
+#pragma unroll
+  for (int r = 0; r < REP; ++r) {
+    const int rc = (r < rep) ? r : rep - 1;
+    const uint16_t* qr =
+        q + ((long)row * hq + (long)g_kv * rep + rc) * D + sub * VEC;
+#pragma unroll
+    for (int w = 0; w < QW; ++w)
+      qbuf[r][w] = reinterpret_cast<const uint4*>(qr)[w];
+  }
+  uint4 kbuf[KPG], vbuf[KPG];
+#pragma unroll
+  for (int i = 0; i < KPG; ++i) {
+    const int j = grp + i * GROUPS;
+    const int jc = (j < cnt) ? j : cnt - 1;
+    kbuf[i] = *reinterpret_cast<const uint4*>(kp + (long)jc * D);
+  }
+#pragma unroll
+  for (int i = 0; i < KPG; ++i) {
+    const int j = grp + i * GROUPS;
+    const int jc = (j < cnt) ? j : cnt - 1;
+    vbuf[i] = *reinterpret_cast<const uint4*>(vp + (long)jc * D);
+  }
+  // keep every load above issued before the first use: left alone, the
+  // scheduler sinks each load to its use to save registers, and a split
+  // then pays one memory latency per key instead of one in all
+  __builtin_amdgcn_sched_barrier(0);
+
+  // scores
+  {
+    float qf[REP][VEC];
+#pragma unroll
+    for (int r = 0; r < REP; ++r)
+#pragma unroll
+      for (int w = 0; w < QW; ++w) {
+        float f[8];
+        ga_unpack(qbuf[r][w], f, (const uint16_t*)nullptr);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) qf[r][8 * w + e] = f[e];
+      }
+#pragma unroll
+    for (int i = 0; i < KPG; ++i) {
+      const int j = grp + i * GROUPS;
+      float kf[VEC];
+      ga_unpack(kbuf[i], kf, (const T*)nullptr);
+#pragma unroll
+      for (int r = 0; r < REP; ++r) {
+        float dot = 0.f;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) dot += qf[r][e] * kf[e];
+#pragma unroll
+        for (int off = LPK / 2; off > 0; off >>= 1)
+          dot += __shfl_xor(dot, off);
+        if (sub == 0 && j < cnt) s_p[r][j] = dot * scale;
+      }
+    }
+  }
+  __syncthreads();
+
+  // softmax over the split's keys: wave w takes heads w, w + 4
+  for (int r = wave; r < REP; r += 4) {
+    float m = -INFINITY;
+    for (int j = lane; j < cnt; j += 64) m = fmaxf(m, s_p[r][j]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    float l = 0.f;
+    for (int j = lane; j < cnt; j += 64) {
+      const float p = __expf(s_p[r][j] - m);
+      s_p[r][j] = p;
+      l += p;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) l += __shfl_xor(l, off);
+    if (lane == 0) {
+      s_ml[r][0] = m;
+      s_ml[r][1] = l;
+    }
+  }
+  __syncthreads();
+
+  // p * V
+  float acc[REP][VEC];
+#pragma unroll
+  for (int r = 0; r < REP; ++r)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) acc[r][e] = 0.f;
+#pragma unroll
+  for (int i = 0; i < KPG; ++i) {
+    const int j = grp + i * GROUPS;
+    if (j < cnt) {
+      float vf[VEC];
+      ga_unpack(vbuf[i], vf, (const T*)nullptr);
+#pragma unroll
+      for (int r = 0; r < REP; ++r) {
+        const float p = s_p[r][j];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[r][e] += p * vf[e];
+      }
+    }
+  }
+  // across the groups of a wave, then across the waves
+#pragma unroll
+  for (int r = 0; r < REP; ++r)
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      float a = acc[r][e];
+#pragma unroll
+      for (int off = LPK; off < 64; off <<= 1) a += __shfl_xor(a, off);
+      acc[r][e] = a;
+    }
+  if (lane < LPK) {
+#pragma unroll
+    for (int r = 0; r < REP; ++r)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) s_acc[wave][r][lane * VEC + e] = acc[r][e];
+  }
+  __syncthreads();
+  for (int idx = tid; idx < rep * D; idx += GA_THREADS) {
+    const int r = idx / D;
+    const int e = idx % D;
+    const float a =
+        ((s_acc[0][r][e] + s_acc[1][r][e]) + s_acc[2][r][e]) + s_acc[3][r][e];
+    float* part = ws + (((long)row * hq + (long)g_kv * rep + r) * n_splits +
+                        split) * (D + GA_WS_PAD);
+    part[GA_WS_PAD + e] = a;
+    if (e < 2) part[e] = s_ml[r][e];
+  }
+}
+
+template <int D>
+__device__ __forceinline__ void ga_combine_body(
+    const float* __restrict__ ws, const long* __restrict__ pos,
+    uint16_t* __restrict__ out, int hq, long max_len, int n_splits) {
+  const int head = blockIdx.x;
+  const int row = blockIdx.y;
+  const int e = threadIdx.x;  // blockDim.x == D
+  long n = pos[row] + 1;
+  if (n > max_len) n = max_len;
+  const int used = (n <= 0) ? 0 : (int)((n + GA_SPLIT - 1) / GA_SPLIT);
+  const float* part =
+      ws + ((long)row * hq + head) * n_splits * (D + GA_WS_PAD);
+  constexpr int STRIDE = D + GA_WS_PAD;
+  // The row's maximum first (lane t reads the m of splits t, t + D, ...;
+  // a max does not depend on the order), so that the loads of the second
+  // pass are independent of each other and can be in flight together:
+  // one load latency per split was most of this kernel's time.
+  __shared__ float s_m[(D + 63) / 64];
+  float m = -INFINITY;
+  for (int s = e; s < used; s += D) m = fmaxf(m, part[(long)s * STRIDE]);
+#pragma unroll
+  for (int off = (D < 64 ? D : 64) / 2; off > 0; off >>= 1)
+    m = fmaxf(m, __shfl_xor(m, off));
+  if constexpr (D > 64) {
+    if ((e & 63) == 0) s_m[e >> 6] = m;
+    __syncthreads();
+    m = s_m[0];
+#pragma unroll
+    for (int w = 1; w < D / 64; ++w) m = fmaxf(m, s_m[w]);
+  }
+  // every lane computes the same l, in ascending split order
+  float l = 0.f, o = 0.f;
+#pragma unroll 8
+  for (int s = 0; s < used; ++s) {
+    const float c = __expf(part[(long)s * STRIDE] - m);
+    l += part[(long)s * STRIDE + 1] * c;
+    o += part[(long)s * STRIDE + GA_WS_PAD + e] * c;
+  }
+  const float r = (used > 0) ? o / l : 0.f;
+  out[((long)row * hq + head) * D + e] =
+      __bfloat16_as_ushort(__float2bfloat16(r));
+}
+
+}  // namespace
+
+template <typename T, int D, int REP>
+__global__ void __launch_bounds__(GA_THREADS)
+gqa_decode_split_kernel(const uint16_t* __restrict__ q,
+                        const T* __restrict__ ck, const T* __restrict__ cv,
+                        const long* __restrict__ pos, float* __restrict__ ws,
+                        int hq, int hk, int rep, float scale, long max_len,
+                        long cache_len, int n_splits) {
+  ga_split_body<T, D, REP>(q, ck, cv, pos, ws, hq, hk, rep, scale, max_len,
+                           cache_len, n_splits);
+}
+
+template <int D>
+__global__ void gqa_decode_combine_kernel(const float* __restrict__ ws,
+                                          const long* __restrict__ pos,
+                                          uint16_t* __restrict__ out, int hq,
+                                          long max_len, int n_splits) {
+  ga_combine_body<D>(ws, pos, out, hq, max_len, n_splits);
+}
+
+namespace {
+
+inline bool ga_shape_ok(int hq, int hk, int d) {
+  if (d != 16 && d != 32 && d != 64 && d != 128) return false;
+  if (hq <= 0 || hk <= 0 || hq % hk != 0 || hq / hk > 8) return false;
+  return true;
+}
+
+inline long ga_n_splits(long max_len) {
+  return (max_len + GA_SPLIT - 1) / GA_SPLIT;
+}
+
+template <typename T, int D>
+hipError_t ga_launch(const void* q, const void* ck, const void* cv,
+                     const void* pos, void* out, void* ws, int b, int hq,
+                     int hk, float scale, long max_len, long cache_len,
+                     hipStream_t stream) {
+  const int rep = hq / hk;
+  const int n_splits = (int)ga_n_splits(max_len);
+  const dim3 grid((uint32_t)n_splits, (uint32_t)hk, (uint32_t)b);
+#define GA_LAUNCH(REP)                                                       \
+  hipLaunchKernelGGL((gqa_decode_split_kernel<T, D, REP>), grid,             \
+                     dim3(GA_THREADS), 0, stream, (const uint16_t*)q,        \
+                     (const T*)ck, (const T*)cv, (const long*)pos,           \
+                     (float*)ws, hq, hk, rep, scale, max_len, cache_len,     \
+                     n_splits)
+  if (rep == 1) GA_LAUNCH(1);
+  else if (rep == 2) GA_LAUNCH(2);
+  else if (rep <= 4) GA_LAUNCH(4);
+  else GA_LAUNCH(8);
+#undef GA_LAUNCH
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((gqa_decode_combine_kernel<D>),
+                     dim3((uint32_t)hq, (uint32_t)b), dim3(D), 0, stream,
+                     (const float*)ws, (const long*)pos, (uint16_t*)out, hq,
+                     max_len, n_splits);
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t ga_launch_d(int d, const void* q, const void* ck, const void* cv,
+                       const void* pos, void* out, void* ws, int b, int hq,
+                       int hk, float scale, long max_len, long cache_len,
+                       hipStream_t stream) {
+  switch (d) {
+    case 16:
+      return ga_launch<T, 16>(q, ck, cv, pos, out, ws, b, hq, hk, scale,
+                              max_len, cache_len, stream);
+    case 32:
+      return ga_launch<T, 32>(q, ck, cv, pos, out, ws, b, hq, hk, scale,
+                              max_len, cache_len, stream);
+    case 64:
+      return ga_launch<T, 64>(q, ck, cv, pos, out, ws, b, hq, hk, scale,
+                              max_len, cache_len, stream);
+    default:
+      return ga_launch<T, 128>(q, ck, cv, pos, out, ws, b, hq, hk, scale,
+                               max_len, cache_len, stream);
+  }
+}
+
+}  // namespace
+
+// bytes of fp32 workspace ca_gqa_decode_attention needs; 0 for an
+// unsupported shape
+extern "C" long ca_gqa_decode_attention_workspace_bytes(int b, int hq, int d,
+                                                        long max_len) {
+  if (b < 0 || hq <= 0 || d <= 0 || max_len <= 0) return 0;
+  return (long)b * hq * ga_n_splits(max_len) * (d + GA_WS_PAD) *
+         (long)sizeof(float);
+}
+
+// q/out [b, hq, d] bf16; ck/cv [b, hk, cache_len, d] bf16 bits, or e4m3
+// codes with kv_fp8; pos [b] int64 on the device.
+extern "C" hipError_t ca_gqa_decode_attention(
+    const void* q, const void* ck, const void* cv, const void* pos, void* out,
+    void* ws, long ws_bytes, int b, int hq, int hk, int d, float scale,
+    long max_len, long cache_len, int kv_fp8, hipStream_t stream) {
+  if (b < 0 || !ga_shape_ok(hq, hk, d)) return hipErrorInvalidValue;
+  if (max_len <= 0 || max_len > cache_len) return hipErrorInvalidValue;
+  if (b > 65535 || hk > 65535) return hipErrorInvalidValue;  // grid y, z
+  if (b == 0) return hipSuccess;
+  if (ws_bytes < ca_gqa_decode_attention_workspace_bytes(b, hq, d, max_len))
+    return hipErrorInvalidValue;
+  // 16-byte q and K/V row loads; fp32 workspace
+  if (((uintptr_t)ck | (uintptr_t)cv | (uintptr_t)q) % 16 != 0 ||
+      (uintptr_t)ws % 4 != 0 || (uintptr_t)out % 2 != 0)
+    return hipErrorInvalidValue;
+  if (kv_fp8)
+    return ga_launch_d<uint8_t>(d, q, ck, cv, pos, out, ws, b, hq, hk, scale,
+                                max_len, cache_len, stream);
+  return ga_launch_d<uint16_t>(d, q, ck, cv, pos, out, ws, b, hq, hk, scale,
+                               max_len, cache_len, stream);
+}
+
 // Skinny decode GEMM: y[8, N] = x[8, K] @ W[N, K]^T, bf16 in/out,
 // fp32 accumulate. The decode batch is tiny (8 rows), so the GEMM is
 // pure weight streaming — hipBLASLt's skinny-tile kernels measured

@@ -13,7 +13,8 @@ import threading
 
 
 def build_core(model_names, device="cuda:0", dtype="bf16",
-               decode_max_batch=8, prewarm_sampling=False):
+               decode_max_batch=8, prewarm_sampling=False,
+               kv_cache_dtype=None):
     from . import (
         AddSubModel,
         IdentityModel,
@@ -122,7 +123,8 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
                 GenerateModel(name, module, device=device,
                               dtype=tdt if use_gpu else None,
                               max_batch=decode_max_batch,
-                              prewarm_sampling=prewarm_sampling)
+                              prewarm_sampling=prewarm_sampling,
+                              kv_cache_dtype=kv_cache_dtype)
             )
         elif name == "ensemble_image":
             # preprocess (HIP kernel on GPU) -> resnet50 pipeline; the
@@ -166,14 +168,7 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
     return core
 
 
-def main(argv=None):
-    import os
-
-    # fast MIOpen kernel selection: skip exhaustive conv tuning at start
-    os.environ.setdefault("MIOPEN_FIND_MODE", "FAST")
-    # dmabuf IPC is the only mode the host driver supports; must be set
-    # before the HIP runtime initializes or hipIpc* fails EINVAL
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+def build_parser():
     parser = argparse.ArgumentParser("client_amd.server")
     parser.add_argument("--http-port", type=int, default=0,
                         help="0 disables HTTP")
@@ -196,15 +191,33 @@ def main(argv=None):
                              "decode and prefill hipGraphs at start-up "
                              "(otherwise captured on the first sampled "
                              "request)")
+    parser.add_argument("--kv-cache-dtype", default="bf16",
+                        choices=["bf16", "fp8_e4m3"],
+                        help="KV-cache storage of generate models: bf16 "
+                             "keeps the model dtype, fp8_e4m3 stores e4m3 "
+                             "codes (half the bytes) read by the fused "
+                             "decode-attention kernel")
     parser.add_argument("--model-warmup", action="store_true",
                         help="pre-capture hipGraphs / prime MIOpen for the "
                              "serving batch sizes before READY is printed")
-    args = parser.parse_args(argv)
+    return parser
+
+
+def main(argv=None):
+    import os
+
+    # fast MIOpen kernel selection: skip exhaustive conv tuning at start
+    os.environ.setdefault("MIOPEN_FIND_MODE", "FAST")
+    # dmabuf IPC is the only mode the host driver supports; must be set
+    # before the HIP runtime initializes or hipIpc* fails EINVAL
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    args = build_parser().parse_args(argv)
 
     core = build_core(
         [m for m in args.models.split(",") if m], args.device, args.dtype,
         decode_max_batch=args.decode_max_batch,
         prewarm_sampling=args.prewarm_sampling,
+        kv_cache_dtype=args.kv_cache_dtype,
     )
     if args.dynamic_batching:
         for model in core.models.values():

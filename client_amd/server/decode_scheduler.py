@@ -50,14 +50,20 @@ class DecodeScheduler:
 
     def __init__(self, model, max_batch=8, device="cuda:0", dtype=None,
                  use_graph=None, len_bucket=256, prefill_chunk=128,
-                 prefill_rows_per_step=2):
+                 prefill_rows_per_step=2, kv_dtype=None):
         self.model = model
         self.device = device
         self.dtype = dtype if dtype is not None else next(
             model.parameters()
         ).dtype
         self.max_batch = max_batch
-        self.kv_cache = model.make_kv_cache(max_batch, device, self.dtype)
+        # None / "bf16": cache in the model dtype; "fp8_e4m3": uint8
+        # e4m3 codes (models/kv_cache.py). The forwards dispatch on the
+        # cache dtype, so capture, prewarm and the sampled variants are
+        # the same code in either mode.
+        self.kv_dtype = kv_dtype
+        self.kv_cache = model.make_kv_cache(max_batch, device, self.dtype,
+                                            kv_dtype)
         self.slots = [_Slot() for _ in range(max_batch)]
         # hipGraph capture of the decode step: pad max_len to fixed
         # buckets so every shape is static; the mask makes the padding

@@ -208,6 +208,8 @@ class GrpcServer:
             o.data_type = _DT_ENUM.get(d, 0)
             o.dims.extend(s)
         cfg.model_transaction_policy.decoupled = model.decoupled
+        for key, value in model.config().get("parameters", {}).items():
+            cfg.parameters[key].string_value = value["string_value"]
         # load-time config override is visible in the served config
         # (same semantics as the HTTP config route)
         override = self.core.config_overrides.get(model.name, {})

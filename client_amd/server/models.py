@@ -261,10 +261,15 @@ class GenerateModel(Model):
     Optional per-request sampling inputs, each of shape [1]:
     ``temperature`` FP32 (default 0 = greedy), ``top_k`` INT32 (0 = off),
     ``top_p`` FP32 (1 = off) and ``seed`` UINT64 (random when absent).
-    A request without any of them decodes greedily."""
+    A request without any of them decodes greedily.
+
+    ``kv_cache_dtype`` None / "bf16" keeps the KV cache in the model
+    dtype; "fp8_e4m3" stores it as e4m3 codes (models/kv_cache.py), and
+    the served config then carries a ``kv_cache_dtype`` parameter."""
 
     def __init__(self, name, llama_module, device="cuda:0", dtype=None,
-                 use_scheduler=True, max_batch=8, prewarm_sampling=False):
+                 use_scheduler=True, max_batch=8, prewarm_sampling=False,
+                 kv_cache_dtype=None):
         super().__init__(
             name,
             [("input_ids", "INT64", [-1]), ("max_tokens", "INT32", [1]),
@@ -276,8 +281,11 @@ class GenerateModel(Model):
         )
         import torch
 
+        from ..models.kv_cache import normalize_kv_dtype
+
         self._torch = torch
         self.device = device
+        self.kv_cache_dtype = normalize_kv_dtype(kv_cache_dtype)
         self.module = llama_module.to(device)
         if dtype is not None:
             self.module = self.module.to(dtype)
@@ -287,7 +295,8 @@ class GenerateModel(Model):
             from .decode_scheduler import DecodeScheduler
 
             self._scheduler = DecodeScheduler(
-                self.module, max_batch=max_batch, device=device
+                self.module, max_batch=max_batch, device=device,
+                kv_dtype=self.kv_cache_dtype,
             )
             # capture the first decode-graph buckets now, not inside the
             # first request's TTFT (cold capture ≈0.5 s per bucket).
@@ -296,6 +305,13 @@ class GenerateModel(Model):
             # the 512-token soak).
             self._scheduler.prewarm(n_buckets=4,
                                     sampling=prewarm_sampling)
+
+    def config(self):
+        cfg = super().config()
+        if self.kv_cache_dtype is not None:
+            cfg["parameters"] = {
+                "kv_cache_dtype": {"string_value": self.kv_cache_dtype}}
+        return cfg
 
     def load_metrics(self):
         """ORCA named metrics for the endpoint-load-metrics header."""
@@ -364,7 +380,8 @@ class GenerateModel(Model):
         if sampling is not None and sampling.is_greedy:
             sampling = None
         for idx, tok in enumerate(
-                self.module.generate(input_ids, max_tokens, sampling)):
+                self.module.generate(input_ids, max_tokens, sampling,
+                                     kv_dtype=self.kv_cache_dtype)):
             yield {
                 "token_id": tok.detach().cpu().numpy().astype(np.int64),
                 "index": np.array([idx], dtype=np.int32),
