@@ -210,12 +210,113 @@ class BiasResAct(nn.Module):
         return out.relu_()
 
 
+# (C_in, C_out, H, W, stride) of the 3x3 convs that run on the fused
+# conv3x3 kernel: the shapes at which it beat conv2 -> BiasAct at batch 8
+# and batch 32 (scripts/bench_conv3x3.py; docs/PERFORMANCE.md). Every
+# other shape keeps the library conv and the BiasAct pass; so does
+# 512 @ 14x14 stride 2, which the kernel runs 40 % faster at batch 32
+# but no faster at batch 8 (56 workgroups).
+CONV3X3_TABLE = frozenset({
+    (64, 64, 56, 56, 1),
+    (128, 128, 56, 56, 2),
+    (128, 128, 28, 28, 1),
+    (256, 256, 28, 28, 2),
+    (256, 256, 14, 14, 1),
+    (512, 512, 7, 7, 1),
+})
+
+
+def pack_conv3x3_weight(weight):
+    """[K, C, 3, 3] -> [3, 3, C/16, K, 16] contiguous: the order in which
+    the conv3x3 kernel's MFMA A fragments (32 output channels x 16 input
+    channels of one tap) are 1 KB contiguous runs."""
+    k, c = weight.shape[:2]
+    return (weight.detach().reshape(k, c // 16, 16, 3, 3)
+            .permute(3, 4, 1, 0, 2).contiguous())
+
+
+class Conv3x3BiasAct(nn.Module):
+    """conv2 -> BiasAct of a bottleneck as ONE CDNA4 kernel: 3x3 conv
+    (pad 1, stride 1 or 2) on the matrix cores reading and writing NCHW,
+    with the bias + ReLU epilogue applied from the accumulators. The
+    library path wraps each of these convs in NCHW<->NHWC transposes of
+    input, output and (every call) weights, accumulates split-K partial
+    sums with atomics in a zeroed fp32 workspace, casts it back, and is
+    followed by the BiasAct pass.
+
+    The module owns no parameters: it is handed the bottleneck's conv2
+    and ba2, and keeps the weights repacked for the kernel in a device
+    buffer keyed on the weight's storage and version, built on the first
+    GPU call (before hipGraph capture: the eager warm-up passes run
+    first). `eligible` says whether a call can take the kernel; the
+    caller falls back to conv2 -> ba2 otherwise."""
+
+    def __init__(self):
+        super().__init__()
+        self._packed = None
+        self._key = None
+        self.calls = 0  # kernel launches (tests assert it really ran)
+
+    @staticmethod
+    def eligible(x, conv):
+        import torch
+
+        if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
+                and x.is_contiguous()):
+            return False
+        if (os.environ.get("CLIENT_AMD_FUSED_BIAS", "1") == "0"
+                or os.environ.get("CLIENT_AMD_CONV3X3", "1") == "0"):
+            return False
+        w = conv.weight
+        if not (conv.bias is None and conv.kernel_size == (3, 3)
+                and conv.padding == (1, 1) and conv.dilation == (1, 1)
+                and conv.groups == 1 and conv.stride in ((1, 1), (2, 2))
+                and conv.padding_mode == "zeros"
+                and w.dtype == torch.bfloat16 and w.device == x.device):
+            return False
+        return (w.shape[1], w.shape[0], x.shape[2], x.shape[3],
+                conv.stride[0]) in CONV3X3_TABLE
+
+    def _weights(self, w):
+        try:
+            version = w._version
+        except RuntimeError:  # inference tensors track no version
+            version = 0
+        key = (w.data_ptr(), version)
+        if self._key != key:
+            self._packed = pack_conv3x3_weight(w)
+            self._key = key
+        return self._packed
+
+    def forward(self, x, conv, ba):
+        import torch
+
+        from ..ops import hip_runtime as hr
+
+        if ba.bias.dtype != torch.float32:
+            # TorchModel's .to(bf16) sweeps buffers; kernel reads fp32
+            ba.bias.data = ba.bias.data.float()
+        n, c, h, w = x.shape
+        k = conv.weight.shape[0]
+        s = conv.stride[0]
+        out = torch.empty((n, k, (h - 1) // s + 1, (w - 1) // s + 1),
+                          device=x.device, dtype=x.dtype)
+        hr.conv3x3_bias_act_bf16(
+            x.data_ptr(), self._weights(conv.weight).data_ptr(),
+            ba.bias.data_ptr(), out.data_ptr(), n, c, k, h, w, s,
+            ba.relu_flag, torch.cuda.current_stream().cuda_stream)
+        self.calls += 1
+        return out
+
+
 class FusedBottleneck(nn.Module):
     """Bottleneck with BN folded into the convs and every elementwise
     epilogue fused into one-pass CDNA4 kernels:
 
         conv1 -> BiasAct(relu)     1 pass  (was bias add + relu = 2)
-        conv2 -> BiasAct(relu)     1 pass
+        conv2 -> BiasAct(relu)     1 pass; one Conv3x3BiasAct kernel for
+                                   the shapes in CONV3X3_TABLE
+                                   (CLIENT_AMD_CONV3X3=0 disables)
         conv3 (biasless), identity = downsample conv (biasless) or x
               -> BiasResAct        1 pass  (was bias [+ds bias] + add
                                             + relu = 3-4 passes)
@@ -230,11 +331,15 @@ class FusedBottleneck(nn.Module):
         self.conv3 = conv3
         self.ds_conv = ds_conv
         self.exit = BiasResAct(exit_bias)
+        self.conv3x3 = Conv3x3BiasAct()
 
     def forward(self, x):
         identity = self.ds_conv(x) if self.ds_conv is not None else x
         out = self.ba1(self.conv1(x))
-        out = self.ba2(self.conv2(out))
+        if Conv3x3BiasAct.eligible(out, self.conv2):
+            out = self.conv3x3(out, self.conv2, self.ba2)
+        else:
+            out = self.ba2(self.conv2(out))
         out = self.conv3(out)
         return self.exit(out, identity)
 

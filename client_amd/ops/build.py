@@ -15,6 +15,9 @@ from pathlib import Path
 OPS_DIR = Path(__file__).resolve().parent
 SRC = OPS_DIR / "csrc" / "hip_runtime.cpp"
 KERNELS = OPS_DIR / "csrc" / "kernels.hip"
+# files kernels.hip #includes
+KERNEL_INCLUDES = (OPS_DIR / "csrc" / "conv3x3.hip",
+                   OPS_DIR / "csrc" / "conv3x3_index.h")
 OUT = OPS_DIR / "_hip_c.so"
 
 GFX_ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
@@ -33,7 +36,7 @@ def _source_hash():
     import hashlib
 
     h = hashlib.sha256()
-    for p in (SRC, KERNELS):
+    for p in (SRC, KERNELS, *KERNEL_INCLUDES):
         h.update(p.read_bytes())
     h.update(GFX_ARCH.encode())
     return h.hexdigest()

@@ -18,6 +18,8 @@
 //     OpenCV path)
 //   - bias_act_bf16 / bias_res_act_bf16 / bias_res_act_cl_bf16 /
 //     bias_relu_maxpool_bf16 (ResNet50 conv epilogues, NCHW and NHWC)
+//   - conv3x3_bias_act_bf16 (ResNet50 bottleneck 3x3 conv + bias + ReLU
+//     on the matrix cores, NCHW)
 //   - rmsnorm_bf16 / rope_decode_bf16 / rope_scatter_decode_bf16 /
 //     decode_gemm_bf16 / sample_logits_bf16 (LLM decode step)
 //   - rope_scatter_decode_fp8kv_bf16 (the same scatter into an e4m3 KV
@@ -325,6 +327,21 @@ static void bias_act_bf16(uintptr_t x, uintptr_t bias, uintptr_t out,
                              reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
+static void conv3x3_bias_act_bf16(uintptr_t x, uintptr_t w_packed,
+                                  uintptr_t bias, uintptr_t out, int n, int c,
+                                  int k, int h, int w, int stride, bool relu,
+                                  uintptr_t stream_handle) {
+  HIP_CHECK(ca_conv3x3_bias_act_bf16(
+      cptr(x), cptr(w_packed), cptr(bias), mptr(out), n, c, k, h, w, stride,
+      relu ? 1 : 0, reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
+// true when ca_conv3x3_bias_act_bf16 accepts the shape (host-side check)
+static bool conv3x3_supported(int n, int c, int k, int h, int w, int stride) {
+  Conv3x3Geom g;
+  return c3_plan(&g, n, c, k, h, w, stride);
+}
+
 static void decode_gemm_bf16(uintptr_t x, uintptr_t w, uintptr_t y, int n,
                              int k, uintptr_t stream_handle) {
   HIP_CHECK(ca_decode_gemm_bf16(
@@ -495,6 +512,12 @@ PYBIND11_MODULE(_hip_c, m) {
   m.def("bias_act_bf16", &bias_act_bf16, py::arg("x"), py::arg("bias"),
         py::arg("out"), py::arg("n_planes"), py::arg("plane"),
         py::arg("channels"), py::arg("relu"), py::arg("stream_handle"));
+  m.def("conv3x3_bias_act_bf16", &conv3x3_bias_act_bf16, py::arg("x"),
+        py::arg("w_packed"), py::arg("bias"), py::arg("out"), py::arg("n"),
+        py::arg("c"), py::arg("k"), py::arg("h"), py::arg("w"),
+        py::arg("stride"), py::arg("relu"), py::arg("stream_handle"));
+  m.def("conv3x3_supported", &conv3x3_supported, py::arg("n"), py::arg("c"),
+        py::arg("k"), py::arg("h"), py::arg("w"), py::arg("stride"));
   m.def("bias_res_act_bf16", &bias_res_act_bf16, py::arg("x"), py::arg("res"),
         py::arg("bias"), py::arg("out"), py::arg("n_planes"), py::arg("plane"),
         py::arg("channels"), py::arg("relu"), py::arg("stream_handle"));

@@ -2073,6 +2073,9 @@ extern "C" hipError_t ca_bias_act_bf16(const void* x, const void* bias,
                               channels, do_relu, stream);
 }
 
+// fused 3x3 conv + bias + ReLU (shares epilogue_finish with the above)
+#include "conv3x3.hip"
+
 // Channels-LAST (NHWC-contiguous) variant: channel is the fastest
 // dim, so each lane's 8 consecutive elements are 8 consecutive
 // channels — loads of x, residual AND bias all coalesce. This is what

@@ -48,6 +48,14 @@ hipError_t ca_bias_res_act_bf16(const void* x, const void* res,
                                 const void* bias, void* out, long n_planes,
                                 long plane, int channels, int do_relu,
                                 hipStream_t stream);
+// fused 3x3 conv (pad 1, stride 1|2) + bias[k] + optional ReLU, NCHW bf16,
+// out of place; w_packed is [3][3][C/16][K][16] bf16, bias fp32. Returns
+// hipErrorInvalidValue, without a launch, for shapes it does not support
+// (C % 32, K % 64, output rows wider than 64, footprint larger than LDS).
+hipError_t ca_conv3x3_bias_act_bf16(const void* x, const void* w_packed,
+                                    const void* bias, void* out, int N, int C,
+                                    int K, int H, int W, int stride,
+                                    int do_relu, hipStream_t stream);
 // ... over a channels-last (NHWC) tensor of n elements; channels % 8 == 0
 hipError_t ca_bias_res_act_cl_bf16(const void* x, const void* res,
                                    const void* bias, void* out, long n,
