@@ -42,6 +42,13 @@ _DECODE_GEMM = os.environ.get("CLIENT_AMD_DECODE_GEMM", "0") == "1"
 _FUSED_ATTN = os.environ.get("CLIENT_AMD_FUSED_ATTN", "0") == "1"
 _FUSED_ATTN_HEAD_DIMS = (16, 32, 64, 128)
 
+# Fused prefill chunk (prefill_attention.hip): one RoPE + scatter launch
+# and one MFMA attention launch per layer instead of the torch rope,
+# index_put, index_select, kv_load, repeat_interleave, mask and sdpa.
+# Off by default until the measurements in docs/PERFORMANCE.md say
+# otherwise; LlamaModel.fused_prefill starts from it.
+_FUSED_PREFILL = os.environ.get("CLIENT_AMD_FUSED_PREFILL", "0") == "1"
+
 
 def _fused_attn_supported(n_heads, n_kv_heads, head_dim):
     return (head_dim in _FUSED_ATTN_HEAD_DIMS and n_heads % n_kv_heads == 0
@@ -64,6 +71,28 @@ def _fused_decode_attention(q, ck, cv, pos_rows, max_len):
         q.data_ptr(), ck.data_ptr(), cv.data_ptr(), pos_rows.data_ptr(),
         out.data_ptr(), ws.data_ptr(), ws_bytes, b, H, ck.shape[1], d, 1.0,
         max_len, ck.shape[2], is_fp8_cache(ck),
+        torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+def _fused_prefill_attention(q, ck, cv, pos_rows, row_lens, row_map, max_len):
+    """q [B, C, H, d] bf16 contiguous with 1/sqrt(d) folded in; ck/cv the
+    whole cache tensors; query c of row i attends to the keys
+    j <= min(pos_rows[i] + c, max_len - 1) of cache row row_map[i].
+    Returns [B, C, H, d], zeros for c >= row_lens[i]. Output and
+    workspace are a torch.empty per call (graph-capturable)."""
+    from ..ops import hip_runtime as hr
+
+    b, c, H, d = q.shape
+    out = torch.empty_like(q)
+    ws_bytes = hr.gqa_prefill_attention_workspace_bytes(b, c, H, d, max_len)
+    ws = torch.empty(max(ws_bytes // 4, 1), device=q.device,
+                     dtype=torch.float32)
+    hr.gqa_prefill_attention(
+        q.data_ptr(), ck.data_ptr(), cv.data_ptr(), pos_rows.data_ptr(),
+        row_lens.data_ptr(), row_map.data_ptr(), out.data_ptr(),
+        ws.data_ptr(), ws_bytes, b, c, H, ck.shape[1], d, 1.0, max_len,
+        ck.shape[2], ck.shape[0], is_fp8_cache(ck),
         torch.cuda.current_stream().cuda_stream)
     return out
 
@@ -245,6 +274,9 @@ class LlamaModel(nn.Module):
         self.norm = RMSNorm(cfg.dim, cfg.norm_eps)
         self.lm_head = nn.Linear(cfg.dim, cfg.vocab_size, bias=False)
         self._rope = None
+        # forward_prefill_chunk through the fused HIP kernels (bf16 on a
+        # HIP device, supported head shape); see _FUSED_PREFILL
+        self.fused_prefill = _FUSED_PREFILL
 
     def _get_rope(self, device):
         if self._rope is None or self._rope[0].device != device:
@@ -455,7 +487,20 @@ class LlamaModel(nn.Module):
         Row independence mirrors forward_decode_batch: per-row RoPE
         offsets, per-row causal masks against each row's own history,
         and padded positions scatter K/V to the reserved scratch cache
-        slot that reads never touch."""
+        slot that reads never touch.
+
+        With ``fused_prefill`` set (bf16 on a HIP device, supported head
+        shape) each layer runs the RoPE + scatter kernel and the MFMA
+        attention kernel instead: padded positions then write nothing at
+        all, and their attention output is zero."""
+        if (self.fused_prefill and tokens.is_cuda
+                and self.tok.weight.dtype == torch.bfloat16
+                and _fused_attn_supported(
+                    self.cfg.n_heads, self.cfg.n_kv_heads,
+                    self.cfg.dim // self.cfg.n_heads)):
+            return self._prefill_chunk_fused(tokens, pos_rows, row_lens,
+                                             last_idx, kv_cache, bucket,
+                                             row_map)
         cos, sin = self._get_rope(tokens.device)
         b, c = tokens.shape
         ar_b = torch.arange(b, device=tokens.device)
@@ -521,6 +566,49 @@ class LlamaModel(nn.Module):
             )
             attn = attn.transpose(1, 2).reshape(b, c, -1)
             x = x + block.wo(attn)
+            h = block.ffn_norm(x)
+            x = x + block.w2(F.silu(block.w1(h)) * block.w3(h))
+        x_last = x[ar_b, last_idx]                           # [B, dim]
+        x_last = self.norm(x_last)
+        return self.lm_head(x_last)
+
+    def _prefill_chunk_fused(self, tokens, pos_rows, row_lens, last_idx,
+                             kv_cache, bucket, row_map):
+        """forward_prefill_chunk on the fused kernels: per layer the
+        projections, rope_scatter_prefill (q rotated and scaled in
+        place, k/v into the mapped cache rows), gqa_prefill_attention
+        over the cache in place, and wo. q/k/v stay in the [B, C, h, d]
+        layout the projections produce."""
+        from ..ops import hip_runtime as hr
+
+        cos, sin = self._get_rope(tokens.device)
+        b, c = tokens.shape
+        ar_b = torch.arange(b, device=tokens.device)
+        if row_map is None:
+            row_map = ar_b
+        pos_rows = pos_rows.contiguous()
+        row_lens = row_lens.contiguous()
+        row_map = row_map.contiguous()
+        H, hk = self.cfg.n_heads, self.cfg.n_kv_heads
+        stream = torch.cuda.current_stream().cuda_stream
+        x = self.tok(tokens)                                 # [B, C, dim]
+        for block, (ck, cv) in zip(self.blocks, kv_cache):
+            d = block.head_dim
+            h = block.attn_norm(x)
+            q = block.wq(h).view(b, c, H, d)
+            k = block.wk(h).view(b, c, hk, d)
+            v = block.wv(h).view(b, c, hk, d)
+            scatter = (hr.rope_scatter_prefill_fp8kv_bf16
+                       if is_fp8_cache(ck) else hr.rope_scatter_prefill_bf16)
+            scatter(
+                q.data_ptr(), k.data_ptr(), v.data_ptr(), ck.data_ptr(),
+                cv.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+                pos_rows.data_ptr(), row_lens.data_ptr(),
+                row_map.data_ptr(), b, c, H, hk, d, ck.shape[2],
+                ck.shape[0], q_scale=d ** -0.5, stream_handle=stream)
+            attn = _fused_prefill_attention(q, ck, cv, pos_rows, row_lens,
+                                            row_map, bucket)
+            x = x + block.wo(attn.view(b, c, -1))
             h = block.ffn_norm(x)
             x = x + block.w2(F.silu(block.w1(h)) * block.w3(h))
         x_last = x[ar_b, last_idx]                           # [B, dim]

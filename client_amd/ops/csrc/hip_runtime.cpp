@@ -26,6 +26,11 @@
 //     cache) / gqa_decode_attention + gqa_decode_attention_workspace_bytes
 //     (fused split + combine decode attention over a bf16 or e4m3 cache;
 //     GQA_DECODE_SPLIT is its split size in keys)
+//   - rope_scatter_prefill_bf16 / rope_scatter_prefill_fp8kv_bf16 (RoPE +
+//     scatter of a prefill chunk into mapped cache rows) /
+//     gqa_prefill_attention + gqa_prefill_attention_workspace_bytes
+//     (flash-style MFMA attention of a chunk over the cache in place;
+//     GQA_PREFILL_QTILE / GQA_PREFILL_KTILE are its tile sizes)
 //
 // The cast, pack and preprocess kernels are memory-bound streaming
 // kernels: 16 B/lane vectorized access, 256-thread blocks (4 waves of
@@ -429,6 +434,50 @@ static void gqa_decode_attention(uintptr_t q, uintptr_t ck, uintptr_t cv,
       kv_fp8 ? 1 : 0, reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
+static void rope_scatter_prefill_bf16(
+    uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t ck, uintptr_t cv,
+    uintptr_t cos_tab, uintptr_t sin_tab, uintptr_t pos, uintptr_t row_lens,
+    uintptr_t row_map, int b, int c, int hq, int hk, int d, long cache_len,
+    long cache_rows, float q_scale, uintptr_t stream_handle) {
+  HIP_CHECK(ca_rope_scatter_prefill_bf16(
+      mptr(q), cptr(k), cptr(v), mptr(ck), mptr(cv), cptr(cos_tab),
+      cptr(sin_tab), cptr(pos), cptr(row_lens), cptr(row_map), b, c, hq, hk,
+      d, cache_len, cache_rows, q_scale,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
+static void rope_scatter_prefill_fp8kv_bf16(
+    uintptr_t q, uintptr_t k, uintptr_t v, uintptr_t ck, uintptr_t cv,
+    uintptr_t cos_tab, uintptr_t sin_tab, uintptr_t pos, uintptr_t row_lens,
+    uintptr_t row_map, int b, int c, int hq, int hk, int d, long cache_len,
+    long cache_rows, float q_scale, uintptr_t stream_handle) {
+  HIP_CHECK(ca_rope_scatter_prefill_fp8kv_bf16(
+      mptr(q), cptr(k), cptr(v), mptr(ck), mptr(cv), cptr(cos_tab),
+      cptr(sin_tab), cptr(pos), cptr(row_lens), cptr(row_map), b, c, hq, hk,
+      d, cache_len, cache_rows, q_scale,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
+static long gqa_prefill_attention_workspace_bytes(int b, int c, int hq, int d,
+                                                  long max_len) {
+  return ca_gqa_prefill_attention_workspace_bytes(b, c, hq, d, max_len);
+}
+
+static void gqa_prefill_attention(uintptr_t q, uintptr_t ck, uintptr_t cv,
+                                  uintptr_t pos, uintptr_t row_lens,
+                                  uintptr_t row_map, uintptr_t out,
+                                  uintptr_t workspace, long workspace_bytes,
+                                  int b, int c, int hq, int hk, int d,
+                                  float scale, long max_len, long cache_len,
+                                  long cache_rows, bool kv_fp8,
+                                  uintptr_t stream_handle) {
+  HIP_CHECK(ca_gqa_prefill_attention(
+      cptr(q), cptr(ck), cptr(cv), cptr(pos), cptr(row_lens), cptr(row_map),
+      mptr(out), mptr(workspace), workspace_bytes, b, c, hq, hk, d, scale,
+      max_len, cache_len, cache_rows, kv_fp8 ? 1 : 0,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
 static void image_preprocess(uintptr_t src, uintptr_t dst, int ih, int iw,
                              int oh, int ow, int mode, bool out_bf16,
                              std::vector<float> mean, std::vector<float> stdev,
@@ -561,6 +610,32 @@ PYBIND11_MODULE(_hip_c, m) {
         py::arg("workspace"), py::arg("workspace_bytes"), py::arg("b"),
         py::arg("hq"), py::arg("hk"), py::arg("d"), py::arg("scale"),
         py::arg("max_len"), py::arg("cache_len"), py::arg("kv_fp8"),
+        py::arg("stream_handle"));
+  m.def("rope_scatter_prefill_bf16", &rope_scatter_prefill_bf16,
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("ck"),
+        py::arg("cv"), py::arg("cos_tab"), py::arg("sin_tab"), py::arg("pos"),
+        py::arg("row_lens"), py::arg("row_map"), py::arg("b"), py::arg("c"),
+        py::arg("hq"), py::arg("hk"), py::arg("d"), py::arg("cache_len"),
+        py::arg("cache_rows"), py::arg("q_scale") = 1.0f,
+        py::arg("stream_handle") = 0);
+  m.def("rope_scatter_prefill_fp8kv_bf16", &rope_scatter_prefill_fp8kv_bf16,
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("ck"),
+        py::arg("cv"), py::arg("cos_tab"), py::arg("sin_tab"), py::arg("pos"),
+        py::arg("row_lens"), py::arg("row_map"), py::arg("b"), py::arg("c"),
+        py::arg("hq"), py::arg("hk"), py::arg("d"), py::arg("cache_len"),
+        py::arg("cache_rows"), py::arg("q_scale") = 1.0f,
+        py::arg("stream_handle") = 0);
+  m.attr("GQA_PREFILL_QTILE") = PA_QTILE;
+  m.attr("GQA_PREFILL_KTILE") = PA_KTILE;
+  m.def("gqa_prefill_attention_workspace_bytes",
+        &gqa_prefill_attention_workspace_bytes, py::arg("b"), py::arg("c"),
+        py::arg("hq"), py::arg("d"), py::arg("max_len"));
+  m.def("gqa_prefill_attention", &gqa_prefill_attention, py::arg("q"),
+        py::arg("ck"), py::arg("cv"), py::arg("pos"), py::arg("row_lens"),
+        py::arg("row_map"), py::arg("out"), py::arg("workspace"),
+        py::arg("workspace_bytes"), py::arg("b"), py::arg("c"), py::arg("hq"),
+        py::arg("hk"), py::arg("d"), py::arg("scale"), py::arg("max_len"),
+        py::arg("cache_len"), py::arg("cache_rows"), py::arg("kv_fp8"),
         py::arg("stream_handle"));
   m.def("gather_pack", &gather_pack, py::arg("src"), py::arg("dst"),
         py::arg("elem_size"), py::arg("shape"), py::arg("strides"),

@@ -660,16 +660,21 @@ extern "C" hipError_t ca_rmsnorm_bf16(const void* x, const void* w, void* out,
 namespace {
 
 // Rotates the bf16 pair src[2j], src[2j+1] by the angle (c, s), scales
-// it, and writes it to dst[2j], dst[2j+1] (dst may be src).
+// it, and writes it to dst[2j], dst[2j+1] (dst may be src). The x2
+// products are rounded and the x1 products fused, written out so that
+// every kernel that rotates gives the same bits whatever the compiler
+// would contract around it (the prefill scatter must match the decode
+// scatter bit for bit).
 __device__ __forceinline__ void rope_rotate_pair(const uint16_t* src,
                                                  uint16_t* dst, int j,
                                                  float c, float s,
                                                  float scale) {
   const float x1 = bf16_to_f32(src[2 * j]);
   const float x2 = bf16_to_f32(src[2 * j + 1]);
-  dst[2 * j] = __bfloat16_as_ushort(__float2bfloat16((x1 * c - x2 * s) * scale));
-  dst[2 * j + 1] =
-      __bfloat16_as_ushort(__float2bfloat16((x1 * s + x2 * c) * scale));
+  const float r1 = fmaf(x1, c, -(x2 * s));
+  const float r2 = fmaf(x1, s, x2 * c);
+  dst[2 * j] = __bfloat16_as_ushort(__float2bfloat16(r1 * scale));
+  dst[2 * j + 1] = __bfloat16_as_ushort(__float2bfloat16(r2 * scale));
 }
 
 }  // namespace
@@ -1239,6 +1244,10 @@ extern "C" hipError_t ca_gqa_decode_attention(
   return ga_launch_d<uint16_t>(d, q, ck, cv, pos, out, ws, b, hq, hk, scale,
                                max_len, cache_len, stream);
 }
+
+// prefill-chunk RoPE + scatter and MFMA attention (share rope_rotate_pair,
+// ga_unpack and ga_shape_ok with the above)
+#include "prefill_attention.hip"
 
 // Skinny decode GEMM: y[8, N] = x[8, K] @ W[N, K]^T, bf16 in/out,
 // fp32 accumulate. The decode batch is tiny (8 rows), so the GEMM is

@@ -14,7 +14,7 @@ import threading
 
 def build_core(model_names, device="cuda:0", dtype="bf16",
                decode_max_batch=8, prewarm_sampling=False,
-               kv_cache_dtype=None):
+               kv_cache_dtype=None, fused_prefill=False):
     from . import (
         AddSubModel,
         IdentityModel,
@@ -124,7 +124,8 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
                               dtype=tdt if use_gpu else None,
                               max_batch=decode_max_batch,
                               prewarm_sampling=prewarm_sampling,
-                              kv_cache_dtype=kv_cache_dtype)
+                              kv_cache_dtype=kv_cache_dtype,
+                              fused_prefill=fused_prefill)
             )
         elif name == "ensemble_image":
             # preprocess (HIP kernel on GPU) -> resnet50 pipeline; the
@@ -197,6 +198,10 @@ def build_parser():
                              "keeps the model dtype, fp8_e4m3 stores e4m3 "
                              "codes (half the bytes) read by the fused "
                              "decode-attention kernel")
+    parser.add_argument("--fused-prefill", action="store_true",
+                        help="run the prefill chunks of generate models on "
+                             "the fused RoPE + scatter and MFMA attention "
+                             "kernels instead of the torch attention block")
     parser.add_argument("--model-warmup", action="store_true",
                         help="pre-capture hipGraphs / prime MIOpen for the "
                              "serving batch sizes before READY is printed")
@@ -218,6 +223,7 @@ def main(argv=None):
         decode_max_batch=args.decode_max_batch,
         prewarm_sampling=args.prewarm_sampling,
         kv_cache_dtype=args.kv_cache_dtype,
+        fused_prefill=args.fused_prefill,
     )
     if args.dynamic_batching:
         for model in core.models.values():

@@ -265,11 +265,15 @@ class GenerateModel(Model):
 
     ``kv_cache_dtype`` None / "bf16" keeps the KV cache in the model
     dtype; "fp8_e4m3" stores it as e4m3 codes (models/kv_cache.py), and
-    the served config then carries a ``kv_cache_dtype`` parameter."""
+    the served config then carries a ``kv_cache_dtype`` parameter.
+
+    ``fused_prefill`` sets the module's ``fused_prefill`` (prefill chunks
+    on the fused HIP kernels, models/llama.py); the served config then
+    carries a ``fused_prefill`` parameter."""
 
     def __init__(self, name, llama_module, device="cuda:0", dtype=None,
                  use_scheduler=True, max_batch=8, prewarm_sampling=False,
-                 kv_cache_dtype=None):
+                 kv_cache_dtype=None, fused_prefill=False):
         super().__init__(
             name,
             [("input_ids", "INT64", [-1]), ("max_tokens", "INT32", [1]),
@@ -290,6 +294,9 @@ class GenerateModel(Model):
         if dtype is not None:
             self.module = self.module.to(dtype)
         self.module.eval()
+        self.fused_prefill = bool(fused_prefill)
+        if self.fused_prefill:
+            self.module.fused_prefill = True
         self._scheduler = None
         if use_scheduler:
             from .decode_scheduler import DecodeScheduler
@@ -308,9 +315,13 @@ class GenerateModel(Model):
 
     def config(self):
         cfg = super().config()
+        params = {}
         if self.kv_cache_dtype is not None:
-            cfg["parameters"] = {
-                "kv_cache_dtype": {"string_value": self.kv_cache_dtype}}
+            params["kv_cache_dtype"] = {"string_value": self.kv_cache_dtype}
+        if self.fused_prefill:
+            params["fused_prefill"] = {"string_value": "true"}
+        if params:
+            cfg["parameters"] = params
         return cfg
 
     def load_metrics(self):
