@@ -18,6 +18,7 @@ import torch.nn.functional as F
 
 from .kv_cache import (is_fp8_cache, kv_load, kv_store,
                        normalize_kv_dtype)
+from .weight_fp8 import Fp8Linear
 
 # Decode attention via grouped bmm instead of materializing K/V per
 # query head: repeat_interleave writes (and re-reads) rep copies of the
@@ -99,7 +100,10 @@ def _fused_prefill_attention(q, ck, cv, pos_rows, row_lens, row_map, max_len):
 
 def _decode_linear(lin, h):
     """h [8, 1, K] -> [8, 1, N] via the skinny decode GEMM kernel when
-    eligible, else the torch linear."""
+    eligible, else the torch linear. An Fp8Linear (weight_fp8.py) picks
+    its own kernel."""
+    if isinstance(lin, Fp8Linear):
+        return lin(h)
     if (_DECODE_GEMM and h.is_cuda and h.dtype == torch.bfloat16
             and h.shape[0] == 8 and h.shape[1] == 1
             and lin.weight.shape[1] % 512 == 0 and lin.bias is None):

@@ -18,7 +18,8 @@ KERNELS = OPS_DIR / "csrc" / "kernels.hip"
 # files kernels.hip #includes
 KERNEL_INCLUDES = (OPS_DIR / "csrc" / "conv3x3.hip",
                    OPS_DIR / "csrc" / "conv3x3_index.h",
-                   OPS_DIR / "csrc" / "prefill_attention.hip")
+                   OPS_DIR / "csrc" / "prefill_attention.hip",
+                   OPS_DIR / "csrc" / "weight_fp8.hip")
 OUT = OPS_DIR / "_hip_c.so"
 
 GFX_ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]

@@ -22,6 +22,7 @@
 //     on the matrix cores, NCHW)
 //   - rmsnorm_bf16 / rope_decode_bf16 / rope_scatter_decode_bf16 /
 //     decode_gemm_bf16 / sample_logits_bf16 (LLM decode step)
+//     fp8w_decode_gemm_bf16 / fp8w_dequant_bf16 (fp8 weight-only linears)
 //   - rope_scatter_decode_fp8kv_bf16 (the same scatter into an e4m3 KV
 //     cache) / gqa_decode_attention + gqa_decode_attention_workspace_bytes
 //     (fused split + combine decode attention over a bf16 or e4m3 cache;
@@ -354,6 +355,22 @@ static void decode_gemm_bf16(uintptr_t x, uintptr_t w, uintptr_t y, int n,
       reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
+static void fp8w_decode_gemm_bf16(uintptr_t x, uintptr_t codes,
+                                  uintptr_t scale_exp, uintptr_t y, int m,
+                                  int n, int k, uintptr_t stream_handle) {
+  HIP_CHECK(ca_fp8w_decode_gemm_bf16(
+      cptr(x), cptr(codes), cptr(scale_exp), mptr(y), m, n, k,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
+static void fp8w_dequant_bf16(uintptr_t codes, uintptr_t scale_exp,
+                              uintptr_t w_out, int n, int k,
+                              uintptr_t stream_handle) {
+  HIP_CHECK(ca_fp8w_dequant_bf16(
+      cptr(codes), cptr(scale_exp), mptr(w_out), n, k,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
 static void bias_res_act_cl_bf16(uintptr_t x, uintptr_t res, uintptr_t bias,
                                  uintptr_t out, long n, int channels,
                                  bool relu, uintptr_t stream_handle) {
@@ -572,6 +589,15 @@ PYBIND11_MODULE(_hip_c, m) {
         py::arg("channels"), py::arg("relu"), py::arg("stream_handle"));
   m.def("decode_gemm_bf16", &decode_gemm_bf16, py::arg("x"), py::arg("w"),
         py::arg("y"), py::arg("n"), py::arg("k"), py::arg("stream_handle"));
+  m.def("fp8w_decode_gemm_bf16", &fp8w_decode_gemm_bf16, py::arg("x"),
+        py::arg("codes"), py::arg("scale_exp"), py::arg("y"), py::arg("m"),
+        py::arg("n"), py::arg("k"), py::arg("stream_handle"));
+  m.def("fp8w_dequant_bf16", &fp8w_dequant_bf16, py::arg("codes"),
+        py::arg("scale_exp"), py::arg("w_out"), py::arg("n"), py::arg("k"),
+        py::arg("stream_handle"));
+  m.attr("FP8W_TILE_ROWS") = FW_ROWS;
+  m.attr("FP8W_TILE_K") = FW_KCHUNK;
+  m.attr("FP8W_MAX_M") = FW_MAX_M;
   m.def("bias_res_act_cl_bf16", &bias_res_act_cl_bf16, py::arg("x"),
         py::arg("res"), py::arg("bias"), py::arg("out"), py::arg("n"),
         py::arg("channels"), py::arg("relu"), py::arg("stream_handle"));

@@ -1348,6 +1348,9 @@ extern "C" hipError_t ca_decode_gemm_bf16(const void* x, const void* w,
   return hipGetLastError();
 }
 
+// fp8 (e4m3) weight-only linears: M <= 16 MFMA decode GEMM and dequant
+#include "weight_fp8.hip"
+
 // Token sampling from bf16 logits: temperature, top-k, top-p and a
 // per-row counter-based random draw, one workgroup per row, placed
 // where argmax sits in the decode step. Every per-row parameter is read

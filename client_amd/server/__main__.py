@@ -14,7 +14,8 @@ import threading
 
 def build_core(model_names, device="cuda:0", dtype="bf16",
                decode_max_batch=8, prewarm_sampling=False,
-               kv_cache_dtype=None, fused_prefill=False):
+               kv_cache_dtype=None, fused_prefill=False,
+               weight_dtype=None):
     from . import (
         AddSubModel,
         IdentityModel,
@@ -125,7 +126,8 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
                               max_batch=decode_max_batch,
                               prewarm_sampling=prewarm_sampling,
                               kv_cache_dtype=kv_cache_dtype,
-                              fused_prefill=fused_prefill)
+                              fused_prefill=fused_prefill,
+                              weight_dtype=weight_dtype)
             )
         elif name == "ensemble_image":
             # preprocess (HIP kernel on GPU) -> resnet50 pipeline; the
@@ -198,6 +200,13 @@ def build_parser():
                              "keeps the model dtype, fp8_e4m3 stores e4m3 "
                              "codes (half the bytes) read by the fused "
                              "decode-attention kernel")
+    parser.add_argument("--weight-dtype", default="bf16",
+                        choices=["bf16", "fp8_e4m3"],
+                        help="block weights of generate models: bf16 keeps "
+                             "the model dtype, fp8_e4m3 stores the "
+                             "projection and FFN weights as e4m3 codes with "
+                             "per-row power-of-two scales (half the bytes) "
+                             "read by the fp8-weight decode GEMM kernel")
     parser.add_argument("--fused-prefill", action="store_true",
                         help="run the prefill chunks of generate models on "
                              "the fused RoPE + scatter and MFMA attention "
@@ -224,6 +233,7 @@ def main(argv=None):
         prewarm_sampling=args.prewarm_sampling,
         kv_cache_dtype=args.kv_cache_dtype,
         fused_prefill=args.fused_prefill,
+        weight_dtype=args.weight_dtype,
     )
     if args.dynamic_batching:
         for model in core.models.values():

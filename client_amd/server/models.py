@@ -267,13 +267,20 @@ class GenerateModel(Model):
     dtype; "fp8_e4m3" stores it as e4m3 codes (models/kv_cache.py), and
     the served config then carries a ``kv_cache_dtype`` parameter.
 
+    ``weight_dtype`` None / "bf16" keeps the block weights in the model
+    dtype; "fp8_e4m3" replaces the seven linears of every block by
+    e4m3 weight-only layers (models/weight_fp8.py) after the device and
+    dtype casts, and the served config then carries a ``weight_dtype``
+    parameter.
+
     ``fused_prefill`` sets the module's ``fused_prefill`` (prefill chunks
     on the fused HIP kernels, models/llama.py); the served config then
     carries a ``fused_prefill`` parameter."""
 
     def __init__(self, name, llama_module, device="cuda:0", dtype=None,
                  use_scheduler=True, max_batch=8, prewarm_sampling=False,
-                 kv_cache_dtype=None, fused_prefill=False):
+                 kv_cache_dtype=None, fused_prefill=False,
+                 weight_dtype=None):
         super().__init__(
             name,
             [("input_ids", "INT64", [-1]), ("max_tokens", "INT32", [1]),
@@ -286,6 +293,8 @@ class GenerateModel(Model):
         import torch
 
         from ..models.kv_cache import normalize_kv_dtype
+        from ..models.weight_fp8 import (normalize_weight_dtype,
+                                         quantize_llama_weights)
 
         self._torch = torch
         self.device = device
@@ -294,6 +303,9 @@ class GenerateModel(Model):
         if dtype is not None:
             self.module = self.module.to(dtype)
         self.module.eval()
+        self.weight_dtype = normalize_weight_dtype(weight_dtype)
+        if self.weight_dtype is not None:
+            quantize_llama_weights(self.module)
         self.fused_prefill = bool(fused_prefill)
         if self.fused_prefill:
             self.module.fused_prefill = True
@@ -318,6 +330,8 @@ class GenerateModel(Model):
         params = {}
         if self.kv_cache_dtype is not None:
             params["kv_cache_dtype"] = {"string_value": self.kv_cache_dtype}
+        if self.weight_dtype is not None:
+            params["weight_dtype"] = {"string_value": self.weight_dtype}
         if self.fused_prefill:
             params["fused_prefill"] = {"string_value": "true"}
         if params:

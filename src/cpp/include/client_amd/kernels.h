@@ -83,6 +83,18 @@ hipError_t ca_rope_scatter_decode_bf16(void* q, const void* k, const void* v,
 // skinny decode GEMM y[8, N] = x[8, K] @ W[N, K]^T, bf16; K % 512 == 0
 hipError_t ca_decode_gemm_bf16(const void* x, const void* w, void* y, int N,
                                int K, hipStream_t stream);
+// fp8 (e4m3) weight-only linear for decode: y[M, N] = x[M, K] @ W_eff^T with
+// W_eff[n, k] = e4m3(codes[n, k]) * 2^scale_exp[n]; x, y bf16, scale_exp int8
+// [N]; codes in the 16-row x 64-k tiled layout of weight_fp8.hip.
+// 1 <= M <= 16, K % 64 == 0, x and codes 16-byte aligned; anything else
+// returns hipErrorInvalidValue without a launch
+hipError_t ca_fp8w_decode_gemm_bf16(const void* x, const void* codes,
+                                    const void* scale_exp, void* y, int M,
+                                    int N, int K, hipStream_t stream);
+// the same codes -> W_eff as row-major [N, K] bf16
+hipError_t ca_fp8w_dequant_bf16(const void* codes, const void* scale_exp,
+                                void* w_out, int N, int K,
+                                hipStream_t stream);
 // token sampling from bf16 logits [rows, vocab]: per-row temperature (f32),
 // top_k (i32), top_p (f32), seed (u64) and step (i64) in device memory;
 // out [rows] int64
