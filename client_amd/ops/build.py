@@ -19,6 +19,7 @@ KERNELS = OPS_DIR / "csrc" / "kernels.hip"
 KERNEL_INCLUDES = (OPS_DIR / "csrc" / "conv3x3.hip",
                    OPS_DIR / "csrc" / "conv3x3_index.h",
                    OPS_DIR / "csrc" / "prefill_attention.hip",
+                   OPS_DIR / "csrc" / "encoder_attention.hip",
                    OPS_DIR / "csrc" / "weight_fp8.hip")
 OUT = OPS_DIR / "_hip_c.so"
 

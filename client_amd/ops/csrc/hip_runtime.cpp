@@ -32,6 +32,9 @@
 //     gqa_prefill_attention + gqa_prefill_attention_workspace_bytes
 //     (flash-style MFMA attention of a chunk over the cache in place;
 //     GQA_PREFILL_QTILE / GQA_PREFILL_KTILE are its tile sizes)
+//   - encoder_attention (BERT self-attention with a per-row key mask, read
+//     in place from the packed qkv projection; ENCODER_ATTN_QTILE /
+//     ENCODER_ATTN_KTILE / ENCODER_ATTN_KSTAGE are its tile sizes)
 //
 // The cast, pack and preprocess kernels are memory-bound streaming
 // kernels: 16 B/lane vectorized access, 256-thread blocks (4 waves of
@@ -495,6 +498,15 @@ static void gqa_prefill_attention(uintptr_t q, uintptr_t ck, uintptr_t cv,
       reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
+static void encoder_attention(uintptr_t qkv, uintptr_t key_mask,
+                              uintptr_t kv_len, uintptr_t out, int b, int s,
+                              int heads, int d, float scale,
+                              uintptr_t stream_handle) {
+  HIP_CHECK(ca_encoder_attention(
+      cptr(qkv), cptr(key_mask), cptr(kv_len), mptr(out), b, s, heads, d,
+      scale, reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
 static void image_preprocess(uintptr_t src, uintptr_t dst, int ih, int iw,
                              int oh, int ow, int mode, bool out_bf16,
                              std::vector<float> mean, std::vector<float> stdev,
@@ -662,6 +674,13 @@ PYBIND11_MODULE(_hip_c, m) {
         py::arg("workspace_bytes"), py::arg("b"), py::arg("c"), py::arg("hq"),
         py::arg("hk"), py::arg("d"), py::arg("scale"), py::arg("max_len"),
         py::arg("cache_len"), py::arg("cache_rows"), py::arg("kv_fp8"),
+        py::arg("stream_handle"));
+  m.attr("ENCODER_ATTN_QTILE") = EA_QTILE;
+  m.attr("ENCODER_ATTN_KTILE") = EA_KTILE;
+  m.attr("ENCODER_ATTN_KSTAGE") = EA_KSTAGE;
+  m.def("encoder_attention", &encoder_attention, py::arg("qkv"),
+        py::arg("key_mask"), py::arg("kv_len"), py::arg("out"), py::arg("b"),
+        py::arg("s"), py::arg("heads"), py::arg("d"), py::arg("scale"),
         py::arg("stream_handle"));
   m.def("gather_pack", &gather_pack, py::arg("src"), py::arg("dst"),
         py::arg("elem_size"), py::arg("shape"), py::arg("strides"),

@@ -1249,6 +1249,10 @@ extern "C" hipError_t ca_gqa_decode_attention(
 // ga_unpack and ga_shape_ok with the above)
 #include "prefill_attention.hip"
 
+// BERT encoder attention with a per-row key mask (shares the fragment
+// types and pa_head_dim_ok with the above)
+#include "encoder_attention.hip"
+
 // Skinny decode GEMM: y[8, N] = x[8, K] @ W[N, K]^T, bf16 in/out,
 // fp32 accumulate. The decode batch is tiny (8 rows), so the GEMM is
 // pure weight streaming — hipBLASLt's skinny-tile kernels measured

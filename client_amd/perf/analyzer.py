@@ -350,6 +350,17 @@ class PerfAnalyzer:
                 httpclient,
             )
 
+    def _optional_inputs(self, client):
+        try:
+            cfg = client.get_model_config(self.model_name)
+        except Exception:
+            return set()
+        if self.protocol == "grpc":
+            return {i.name for i in cfg.config.input if i.optional}
+        cfg = cfg.get("config", cfg)
+        return {i["name"] for i in cfg.get("input", [])
+                if i.get("optional")}
+
     def _model_io(self, client):
         meta = client.get_model_metadata(self.model_name)
         if self.protocol == "grpc":
@@ -360,6 +371,16 @@ class PerfAnalyzer:
                       for i in meta["inputs"]]
             outputs = [(o["name"], o["datatype"], list(o["shape"]))
                        for o in meta["outputs"]]
+
+        # an input the model config marks optional is sent only when the
+        # run names it (--shape NAME:... or --input-data); the workload
+        # of a model that gains one stays what it was
+        optional = self._optional_inputs(client)
+        named = set(self.shapes)
+        for entry in self.input_data or []:
+            named.update(entry)
+        inputs = [i for i in inputs
+                  if i[0] not in optional or i[0] in named]
 
         def concrete(name, shape):
             if name in self.shapes:

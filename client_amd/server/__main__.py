@@ -15,7 +15,7 @@ import threading
 def build_core(model_names, device="cuda:0", dtype="bf16",
                decode_max_batch=8, prewarm_sampling=False,
                kv_cache_dtype=None, fused_prefill=False,
-               weight_dtype=None):
+               weight_dtype=None, bert_fused_attention=False):
     from . import (
         AddSubModel,
         IdentityModel,
@@ -87,11 +87,15 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
             io_dt = {"bf16": "BF16", "fp16": "FP16", "fp32": "FP32"}[dtype]
             module = bert_large() if name == "bert_large" else bert_tiny()
             hidden = 1024 if name == "bert_large" else 32
+            if bert_fused_attention:
+                module.fused_attention = True
             core.add_model(
                 TorchModel(
                     name,
                     module,
-                    inputs=[("input_ids", "INT64", [-1, -1])],
+                    inputs=[("input_ids", "INT64", [-1, -1]),
+                            ("attention_mask", "INT64", [-1, -1])],
+                    optional_inputs=("attention_mask",),
                     outputs=[("pooled", io_dt, [-1, hidden])],
                     device=device,
                     dtype=tdt if device.startswith("cuda") else None,
@@ -211,6 +215,10 @@ def build_parser():
                         help="run the prefill chunks of generate models on "
                              "the fused RoPE + scatter and MFMA attention "
                              "kernels instead of the torch attention block")
+    parser.add_argument("--bert-fused-attention", action="store_true",
+                        help="run the attention of the BERT models on the "
+                             "fused MFMA encoder-attention kernel instead "
+                             "of torch's multi-head attention")
     parser.add_argument("--model-warmup", action="store_true",
                         help="pre-capture hipGraphs / prime MIOpen for the "
                              "serving batch sizes before READY is printed")
@@ -234,6 +242,7 @@ def main(argv=None):
         kv_cache_dtype=args.kv_cache_dtype,
         fused_prefill=args.fused_prefill,
         weight_dtype=args.weight_dtype,
+        bert_fused_attention=args.bert_fused_attention,
     )
     if args.dynamic_batching:
         for model in core.models.values():

@@ -4,7 +4,10 @@ Triton-style request coalescing (the reference's ModelDynamicBatching
 config, model_config.proto / SURVEY.md §2.7): concurrent requests are
 merged along the batch dimension up to ``preferred_batch_size`` (or
 until ``max_queue_delay_us`` expires), executed as one forward, and the
-outputs are split back per request. On the MI355X path both the gather
+outputs are split back per request. Only requests with the same number
+of tensors, dtypes and trailing shapes are merged; the first queued one
+that differs (another sequence length, a request with an optional input
+the others lack) ends the batch and opens the next. On the MI355X path both the gather
 (torch.cat) and the scatter (slice copy_) are device-side — requests
 arriving via HIP-shm never touch the host.
 """
@@ -70,6 +73,12 @@ class DynamicBatcher:
             raise item.error
         return item.outputs, item.done_ev
 
+    @staticmethod
+    def _signature(tensors):
+        """What two requests must share to be merged along dim 0: the
+        number of tensors, their dtypes and their trailing shapes."""
+        return tuple((t.dtype, tuple(t.shape[1:])) for t in tensors)
+
     def shutdown(self):
         with self._cv:
             self._alive = False
@@ -94,6 +103,11 @@ class DynamicBatcher:
                     if self._queue:
                         nxt = self._queue[0]
                         if total + nxt.batch > self._max:
+                            break
+                        if (self._signature(nxt.tensors)
+                                != self._signature(items[0].tensors)):
+                            # cannot be concatenated with this batch: it
+                            # stays at the head for the next one
                             break
                         self._queue.pop(0)
                         items.append(nxt)

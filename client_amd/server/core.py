@@ -506,8 +506,20 @@ class InferenceCore:
             return torch.from_dlpack(smt)
 
         t0 = time.monotonic_ns()
+        # in the order of the model's declared inputs, whatever the
+        # request's order; an absent optional input is left out
+        by_input = {io["name"]: io for io in req_inputs}
+        optional = getattr(model, "optional_inputs", ())
         tensors = []
-        for io in req_inputs:
+        for name, _, _ in model.inputs:
+            io = by_input.get(name)
+            if io is None:
+                if name in optional:
+                    continue
+                raise InferenceError(
+                    f"expected inference input '{name}' for model "
+                    f"'{model.name}'"
+                )
             tensors.append(region_tensor(io, io["datatype"], io["shape"]))
         t1 = time.monotonic_ns()
         if hasattr(model, "execute_torch_async"):

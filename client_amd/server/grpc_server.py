@@ -202,6 +202,8 @@ class GrpcServer:
             i.name = n
             i.data_type = _DT_ENUM.get(d, 0)
             i.dims.extend(s)
+            if n in getattr(model, "optional_inputs", ()):
+                i.optional = True
         for n, d, s in model.outputs:
             o = cfg.output.add()
             o.name = n

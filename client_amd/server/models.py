@@ -542,8 +542,16 @@ class TorchModel(Model):
     """
 
     def __init__(self, name, module, inputs, outputs, device="cuda:0",
-                 dtype=None, max_batch_size=0, use_graph=True):
+                 dtype=None, max_batch_size=0, use_graph=True,
+                 optional_inputs=()):
         super().__init__(name, inputs, outputs, max_batch_size, platform="pytorch")
+        # names of declared inputs a request may leave out; the module is
+        # then called without them (they are its trailing arguments)
+        self.optional_inputs = frozenset(optional_inputs)
+        unknown = self.optional_inputs - {n for n, _, _ in inputs}
+        if unknown:
+            raise ValueError(f"optional inputs {sorted(unknown)} are not "
+                             f"inputs of model '{name}'")
         import threading
 
         import torch
@@ -571,6 +579,16 @@ class TorchModel(Model):
         self._graph_lock = threading.Lock()
         self._batcher = None
 
+    def config(self):
+        cfg = super().config()
+        for entry in cfg["input"]:
+            if entry["name"] in self.optional_inputs:
+                entry["optional"] = True
+        if getattr(self.module, "fused_attention", False):
+            cfg["parameters"] = {
+                "fused_attention": {"string_value": "true"}}
+        return cfg
+
     def enable_dynamic_batching(self, preferred_batch_size=32,
                                 max_queue_delay_us=500, max_batch_size=64):
         """Triton-style dynamic batching in front of the forward."""
@@ -595,6 +613,8 @@ class TorchModel(Model):
         for bs in batch_sizes:
             tensors = []
             for name, datatype, shape in self.inputs:
+                if name in self.optional_inputs:
+                    continue
                 dims = [bs if d == -1 else d for d in shape]
                 if len(shape) > 0 and shape[0] == -1:
                     dims[0] = bs
@@ -613,6 +633,14 @@ class TorchModel(Model):
         with torch.inference_mode():
             tensors = []
             for name, datatype, _ in self.inputs:
+                if name not in inputs:
+                    if name in self.optional_inputs:
+                        continue
+                    from .core import InferenceError
+
+                    raise InferenceError(
+                        f"expected inference input '{name}' for model "
+                        f"'{self.name}'")
                 arr = inputs[name]
                 t = torch.from_numpy(np.ascontiguousarray(arr)).to(self.device)
                 if self.dtype is not None and t.is_floating_point():
