@@ -39,8 +39,7 @@ typedef __attribute__((ext_vector_type(16))) float c3_frag_cd;
 // epilogue of bias_act_bf16_kernel: fp32 bias add, ReLU, RNE
 __device__ __forceinline__ uint16_t c3_finish(float acc, float b,
                                               int do_relu) {
-  const uint16_t h = acc != acc ? (uint16_t)0x7FC0 : f32_to_bf16_rne(acc);
-  return epilogue_finish(bf16_to_f32(h) + b, do_relu);
+  return epilogue_finish(bf16_to_f32(f32_to_bf16_rne(acc)) + b, do_relu);
 }
 
 template <int NT>

@@ -27,11 +27,12 @@ inline int ca_grid_for(long work_items) {
 
 // ---------------------------------------------------------------------------
 // bf16 helpers. Two float -> bf16 roundings live in this file and must
-// not be mixed: truncation for the wire codec, integer round-to-
-// nearest-even for the epilogue, stem and decode-GEMM kernels.
-// rmsnorm_bf16_kernel and the RoPE kernels use neither: they round with
-// the __float2bfloat16 intrinsic, which treats NaN differently (the
-// integer formula can carry an all-ones NaN payload into the sign bit).
+// not be mixed: truncation for the wire codec, round-to-nearest-even
+// everywhere else (the integer formula in the decode-GEMM, attention
+// and conv3x3 kernels, the hardware convert in the epilogue and stem
+// kernels). rmsnorm_bf16_kernel and the RoPE kernels round with the
+// __float2bfloat16 intrinsic. All the RNE forms give a NaN for every
+// NaN; which NaN (payload) is not pinned.
 // ---------------------------------------------------------------------------
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) {
@@ -45,11 +46,32 @@ __device__ __forceinline__ uint16_t f32_to_bf16_trunc(float f) {
   return (uint16_t)(__float_as_uint(f) >> 16);
 }
 
-// round-to-nearest-even (matches torch float->bf16 casts)
+// round-to-nearest-even (matches torch float->bf16 casts). A NaN stays
+// a NaN of its sign, made quiet: the rounding add alone would carry a
+// payload of 0x7F8000 and above (an fp32 bias can hold one, and fp32
+// adds propagate it) through the exponent into the sign bit and store
+// 0x7FFFFFFF as -0.0.
 __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
   uint32_t u = __float_as_uint(f);
+  const uint16_t nan = (uint16_t)((u >> 16) | 0x0040u);
+  const bool is_nan = (u & 0x7FFFFFFFu) > 0x7F800000u;
   u += 0x7FFF + ((u >> 16) & 1);
-  return (uint16_t)(u >> 16);
+  return is_nan ? nan : (uint16_t)(u >> 16);
+}
+
+// The same rounding by gfx950's packed convert (v_cvt_pk_bf16_f32: RNE,
+// NaN stays NaN), one instruction per pair. The bandwidth-bound
+// epilogues use it: there the integer formula with its NaN guard
+// measured 2.5-8 % slower per call than without the guard.
+typedef float ca_f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 ca_bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint16_t f32_to_bf16_cvt(float f) {
+  return __builtin_bit_cast(uint16_t, (__bf16)f);
+}
+// (lo, hi) -> packed u32, low half = lower address
+__device__ __forceinline__ uint32_t f32x2_to_bf16x2_cvt(float lo, float hi) {
+  const ca_f32x2 v = {lo, hi};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, ca_bf16x2));
 }
 
 // the two bf16 halves of a packed u32 (low half = lower address)
@@ -1822,7 +1844,7 @@ namespace {
 // optional ReLU, then RNE back to bf16
 __device__ __forceinline__ uint16_t epilogue_finish(float f, int do_relu) {
   if (do_relu && f < 0.f) f = 0.f;
-  return f32_to_bf16_rne(f);
+  return f32_to_bf16_cvt(f);
 }
 
 // One packed pair of bf16 elements through the epilogue: x (and the
@@ -1839,8 +1861,11 @@ __device__ __forceinline__ uint32_t epilogue_pair(uint32_t xw, uint32_t rw,
     lo += bf16x2_lo(rw);
     hi += bf16x2_hi(rw);
   }
-  return (uint32_t)epilogue_finish(lo + b_lo, do_relu) |
-         ((uint32_t)epilogue_finish(hi + b_hi, do_relu) << 16);
+  lo += b_lo;
+  hi += b_hi;
+  if (do_relu && lo < 0.f) lo = 0.f;
+  if (do_relu && hi < 0.f) hi = 0.f;
+  return f32x2_to_bf16x2_cvt(lo, hi);
 }
 
 // the same for one element of a ragged end (res may be null)
