@@ -166,6 +166,9 @@ class Fp8Linear(nn.Module):
         return (f"in_features={self.in_features}, "
                 f"out_features={self.out_features}, e4m3")
 
+    def weight_bytes(self):
+        return self.codes.numel() + self.scale_exp.numel()
+
     def row_major_codes(self):
         return unpack_codes(self.codes, self.out_features, self.in_features)
 
@@ -210,14 +213,20 @@ class Fp8Linear(nn.Module):
         return F.linear(x, w)
 
 
-def quantize_llama_weights(model):
+def quantize_llama_weights(model, layer_cls=None):
     """Replaces wq, wk, wv, wo, w1, w3 and w2 of every block of a
     LlamaModel in place by Fp8Linear, releasing each bf16 tensor as it
     goes. tok, the norms and lm_head keep the model dtype (logits
     precision; lm_head is 6 % of the 8B model's bytes). On a HIP device
     the shared dequant scratch is allocated here, sized to the largest
     layer. Returns (bytes_before, bytes_after) of the replaced weights,
-    the scratch included in bytes_after."""
+    the scratch included in bytes_after.
+
+    ``layer_cls`` picks another weight-only layer class with the same
+    interface (from_linear(lin, scratch=), weight_bytes(), in_features,
+    out_features), such as weight_mxfp4.Mxfp4Linear."""
+    if layer_cls is None:
+        layer_cls = Fp8Linear
     scratch = _Scratch()
     before = after = 0
     largest = 0
@@ -225,15 +234,15 @@ def quantize_llama_weights(model):
     for block in model.blocks:
         for name in LLAMA_BLOCK_LINEARS:
             lin = getattr(block, name)
-            if isinstance(lin, Fp8Linear):
+            if isinstance(lin, (Fp8Linear, layer_cls)):
                 continue
             w = lin.weight
             device = w.device
             before += w.numel() * w.element_size()
-            q = Fp8Linear.from_linear(lin, scratch=scratch)
+            q = layer_cls.from_linear(lin, scratch=scratch)
             setattr(block, name, q)
             del lin, w
-            after += q.codes.numel() + q.scale_exp.numel()
+            after += q.weight_bytes()
             largest = max(largest, q.in_features * q.out_features)
     if device is not None and device.type == "cuda":
         after += 2 * scratch.reserve(largest, device).numel()

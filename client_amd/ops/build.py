@@ -20,7 +20,8 @@ KERNEL_INCLUDES = (OPS_DIR / "csrc" / "conv3x3.hip",
                    OPS_DIR / "csrc" / "conv3x3_index.h",
                    OPS_DIR / "csrc" / "prefill_attention.hip",
                    OPS_DIR / "csrc" / "encoder_attention.hip",
-                   OPS_DIR / "csrc" / "weight_fp8.hip")
+                   OPS_DIR / "csrc" / "weight_fp8.hip",
+                   OPS_DIR / "csrc" / "weight_mxfp4.hip")
 OUT = OPS_DIR / "_hip_c.so"
 
 GFX_ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]

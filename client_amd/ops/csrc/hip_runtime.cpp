@@ -23,6 +23,8 @@
 //   - rmsnorm_bf16 / rope_decode_bf16 / rope_scatter_decode_bf16 /
 //     decode_gemm_bf16 / sample_logits_bf16 (LLM decode step)
 //     fp8w_decode_gemm_bf16 / fp8w_dequant_bf16 (fp8 weight-only linears)
+//     mxfp4w_decode_gemm_bf16 / mxfp4w_dequant_bf16 (MXFP4 weight-only
+//     linears)
 //   - rope_scatter_decode_fp8kv_bf16 (the same scatter into an e4m3 KV
 //     cache) / gqa_decode_attention + gqa_decode_attention_workspace_bytes
 //     (fused split + combine decode attention over a bf16 or e4m3 cache;
@@ -374,6 +376,22 @@ static void fp8w_dequant_bf16(uintptr_t codes, uintptr_t scale_exp,
       reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
+static void mxfp4w_decode_gemm_bf16(uintptr_t x, uintptr_t codes,
+                                    uintptr_t scales, uintptr_t y, int m,
+                                    int n, int k, uintptr_t stream_handle) {
+  HIP_CHECK(ca_mxfp4w_decode_gemm_bf16(
+      cptr(x), cptr(codes), cptr(scales), mptr(y), m, n, k,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
+static void mxfp4w_dequant_bf16(uintptr_t codes, uintptr_t scales,
+                                uintptr_t w_out, int n, int k,
+                                uintptr_t stream_handle) {
+  HIP_CHECK(ca_mxfp4w_dequant_bf16(
+      cptr(codes), cptr(scales), mptr(w_out), n, k,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
 static void bias_res_act_cl_bf16(uintptr_t x, uintptr_t res, uintptr_t bias,
                                  uintptr_t out, long n, int channels,
                                  bool relu, uintptr_t stream_handle) {
@@ -610,6 +628,15 @@ PYBIND11_MODULE(_hip_c, m) {
   m.attr("FP8W_TILE_ROWS") = FW_ROWS;
   m.attr("FP8W_TILE_K") = FW_KCHUNK;
   m.attr("FP8W_MAX_M") = FW_MAX_M;
+  m.def("mxfp4w_decode_gemm_bf16", &mxfp4w_decode_gemm_bf16, py::arg("x"),
+        py::arg("codes"), py::arg("scales"), py::arg("y"), py::arg("m"),
+        py::arg("n"), py::arg("k"), py::arg("stream_handle"));
+  m.def("mxfp4w_dequant_bf16", &mxfp4w_dequant_bf16, py::arg("codes"),
+        py::arg("scales"), py::arg("w_out"), py::arg("n"), py::arg("k"),
+        py::arg("stream_handle"));
+  m.attr("MXFP4W_ROW_GROUP") = FM_GROUP;
+  m.attr("MXFP4W_TILE_K") = FM_KCHUNK;
+  m.attr("MXFP4W_MAX_M") = FM_MAX_M;
   m.def("bias_res_act_cl_bf16", &bias_res_act_cl_bf16, py::arg("x"),
         py::arg("res"), py::arg("bias"), py::arg("out"), py::arg("n"),
         py::arg("channels"), py::arg("relu"), py::arg("stream_handle"));

@@ -1377,6 +1377,9 @@ extern "C" hipError_t ca_decode_gemm_bf16(const void* x, const void* w,
 // fp8 (e4m3) weight-only linears: M <= 16 MFMA decode GEMM and dequant
 #include "weight_fp8.hip"
 
+// MXFP4 (e2m1 + e8m0 block scales) weight-only linears: the same pair
+#include "weight_mxfp4.hip"
+
 // Token sampling from bf16 logits: temperature, top-k, top-p and a
 // per-row counter-based random draw, one workgroup per row, placed
 // where argmax sits in the decode step. Every per-row parameter is read

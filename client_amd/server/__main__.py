@@ -205,12 +205,15 @@ def build_parser():
                              "codes (half the bytes) read by the fused "
                              "decode-attention kernel")
     parser.add_argument("--weight-dtype", default="bf16",
-                        choices=["bf16", "fp8_e4m3"],
+                        choices=["bf16", "fp8_e4m3", "mxfp4"],
                         help="block weights of generate models: bf16 keeps "
                              "the model dtype, fp8_e4m3 stores the "
                              "projection and FFN weights as e4m3 codes with "
                              "per-row power-of-two scales (half the bytes) "
-                             "read by the fp8-weight decode GEMM kernel")
+                             "read by the fp8-weight decode GEMM kernel, "
+                             "mxfp4 as e2m1 codes with a power-of-two scale "
+                             "per 32 elements (0.53 bytes per weight) read "
+                             "by the MXFP4-weight decode GEMM kernel")
     parser.add_argument("--fused-prefill", action="store_true",
                         help="run the prefill chunks of generate models on "
                              "the fused RoPE + scatter and MFMA attention "

@@ -269,9 +269,9 @@ class GenerateModel(Model):
 
     ``weight_dtype`` None / "bf16" keeps the block weights in the model
     dtype; "fp8_e4m3" replaces the seven linears of every block by
-    e4m3 weight-only layers (models/weight_fp8.py) after the device and
-    dtype casts, and the served config then carries a ``weight_dtype``
-    parameter.
+    e4m3 weight-only layers (models/weight_fp8.py) and "mxfp4" by MXFP4
+    ones (models/weight_mxfp4.py) after the device and dtype casts, and
+    the served config then carries a ``weight_dtype`` parameter.
 
     ``fused_prefill`` sets the module's ``fused_prefill`` (prefill chunks
     on the fused HIP kernels, models/llama.py); the served config then
@@ -293,8 +293,8 @@ class GenerateModel(Model):
         import torch
 
         from ..models.kv_cache import normalize_kv_dtype
-        from ..models.weight_fp8 import (normalize_weight_dtype,
-                                         quantize_llama_weights)
+        from ..models.weight_mxfp4 import (normalize_weight_dtype,
+                                           quantize_llama_weights_as)
 
         self._torch = torch
         self.device = device
@@ -305,7 +305,7 @@ class GenerateModel(Model):
         self.module.eval()
         self.weight_dtype = normalize_weight_dtype(weight_dtype)
         if self.weight_dtype is not None:
-            quantize_llama_weights(self.module)
+            quantize_llama_weights_as(self.module, self.weight_dtype)
         self.fused_prefill = bool(fused_prefill)
         if self.fused_prefill:
             self.module.fused_prefill = True

@@ -95,6 +95,18 @@ hipError_t ca_fp8w_decode_gemm_bf16(const void* x, const void* codes,
 hipError_t ca_fp8w_dequant_bf16(const void* codes, const void* scale_exp,
                                 void* w_out, int N, int K,
                                 hipStream_t stream);
+// MXFP4 weight-only linear for decode: W_eff[n, k] = e2m1(codes[n, k]) *
+// 2^(scales[n, k / 32] - 127); codes and scales in the tiled layout of
+// weight_mxfp4.hip. 1 <= M <= 16, K % 32 == 0, x and codes 16-byte and
+// scales 4-byte aligned; anything else returns hipErrorInvalidValue without
+// a launch
+hipError_t ca_mxfp4w_decode_gemm_bf16(const void* x, const void* codes,
+                                      const void* scales, void* y, int M,
+                                      int N, int K, hipStream_t stream);
+// the same codes and scales -> W_eff as row-major [N, K] bf16
+hipError_t ca_mxfp4w_dequant_bf16(const void* codes, const void* scales,
+                                  void* w_out, int N, int K,
+                                  hipStream_t stream);
 // token sampling from bf16 logits [rows, vocab]: per-row temperature (f32),
 // top_k (i32), top_p (f32), seed (u64) and step (i64) in device memory;
 // out [rows] int64
