@@ -129,13 +129,19 @@ class Fp8Linear(nn.Module):
     """y = x @ W_eff^T, no bias. Buffers ``codes`` (tiled, see the module
     docstring) and ``scale_exp``.
 
-    forward takes one of three routes:
+    forward takes one of four routes:
 
     - decode: HIP device, bf16 x, 1 <= M <= 16 rows after flattening the
       leading dims: the MFMA decode GEMM (fp8w_decode_gemm_bf16), which
       streams the codes once and converts them in registers;
-    - dequant: any other x on a HIP device (prefill chunks, decode
-      batches above 16): fp8w_dequant_bf16 writes W_eff into a bf16
+    - wide: only with ``fused_gemm`` set (default False): HIP device,
+      bf16 x, M > 16 (prefill chunks, decode batches above 16): the
+      tiled MFMA GEMM (fp8w_gemm_bf16), which reads the codes straight
+      into registers and stages x through LDS; no scratch, two bytes per
+      weight less written and read back than the next route;
+    - dequant: any other x on a HIP device (with ``fused_gemm`` off,
+      every M > 16; always other dtypes and a call the kernels reject
+      before launch): fp8w_dequant_bf16 writes W_eff into a bf16
       scratch buffer and F.linear runs on it. The scratch is shared by
       all Fp8Linears of a model and sized to the largest at quantise
       time, so the step stays graph-capturable; sharing it assumes that
@@ -144,11 +150,12 @@ class Fp8Linear(nn.Module):
     - CPU: F.linear on dequantize_weight.
     """
 
-    def __init__(self, codes, scale_exp, scratch=None):
+    def __init__(self, codes, scale_exp, scratch=None, fused_gemm=False):
         super().__init__()
         n, k = codes.shape
         if scale_exp.shape != (n,):
             raise ValueError("scale_exp must be [out_features]")
+        self.fused_gemm = bool(fused_gemm)
         self.in_features = k
         self.out_features = n
         self.register_buffer("codes", pack_codes(codes))
@@ -207,13 +214,26 @@ class Fp8Linear(nn.Module):
             except RuntimeError:
                 # rejected before any launch (a misaligned view of x)
                 pass
+        elif self.fused_gemm and x.dtype == torch.bfloat16 and m > 0:
+            from ..ops import hip_runtime as hr
+
+            x2 = x.reshape(m, k).contiguous()
+            y = torch.empty(m, n, device=x.device, dtype=torch.bfloat16)
+            try:
+                hr.fp8w_gemm_bf16(
+                    x2.data_ptr(), self.codes.data_ptr(),
+                    self.scale_exp.data_ptr(), y.data_ptr(), m, n, k,
+                    torch.cuda.current_stream().cuda_stream)
+                return y.view(*x.shape[:-1], n)
+            except RuntimeError:
+                pass  # as above
         w = self.dequant_to_scratch()
         if w.dtype != x.dtype:
             w = w.to(x.dtype)
         return F.linear(x, w)
 
 
-def quantize_llama_weights(model, layer_cls=None):
+def quantize_llama_weights(model, layer_cls=None, fused_gemm=False):
     """Replaces wq, wk, wv, wo, w1, w3 and w2 of every block of a
     LlamaModel in place by Fp8Linear, releasing each bf16 tensor as it
     goes. tok, the norms and lm_head keep the model dtype (logits
@@ -224,7 +244,11 @@ def quantize_llama_weights(model, layer_cls=None):
 
     ``layer_cls`` picks another weight-only layer class with the same
     interface (from_linear(lin, scratch=), weight_bytes(), in_features,
-    out_features), such as weight_mxfp4.Mxfp4Linear."""
+    out_features), such as weight_mxfp4.Mxfp4Linear.
+
+    ``fused_gemm`` sets Fp8Linear.fused_gemm on the layers created here
+    (M > 16 on fp8w_gemm_bf16 instead of the dequant route); the scratch
+    is reserved all the same, for the fallback."""
     if layer_cls is None:
         layer_cls = Fp8Linear
     scratch = _Scratch()
@@ -240,6 +264,8 @@ def quantize_llama_weights(model, layer_cls=None):
             device = w.device
             before += w.numel() * w.element_size()
             q = layer_cls.from_linear(lin, scratch=scratch)
+            if fused_gemm:
+                q.fused_gemm = True
             setattr(block, name, q)
             del lin, w
             after += q.weight_bytes()

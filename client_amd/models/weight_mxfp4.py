@@ -256,11 +256,16 @@ class Mxfp4Linear(nn.Module):
 LAYER_CLASSES = {"fp8_e4m3": Fp8Linear, "mxfp4": Mxfp4Linear}
 
 
-def quantize_llama_weights_as(model, weight_dtype):
+def quantize_llama_weights_as(model, weight_dtype, fused_gemm=False):
     """quantize_llama_weights with the layer class of ``weight_dtype``
-    ("fp8_e4m3" or "mxfp4")."""
+    ("fp8_e4m3" or "mxfp4"). ``fused_gemm`` (the wide fp8 GEMM for
+    M > 16) exists for "fp8_e4m3" only."""
+    if fused_gemm and weight_dtype != "fp8_e4m3":
+        raise ValueError(f"fused_gemm needs weight_dtype 'fp8_e4m3', not "
+                         f"{weight_dtype!r}")
     return quantize_llama_weights(model,
-                                  layer_cls=LAYER_CLASSES[weight_dtype])
+                                  layer_cls=LAYER_CLASSES[weight_dtype],
+                                  fused_gemm=fused_gemm)
 
 
 __all__ = ["WEIGHT_DTYPES", "LLAMA_BLOCK_LINEARS", "LAYER_CLASSES",

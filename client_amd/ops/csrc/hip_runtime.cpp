@@ -22,7 +22,8 @@
 //     on the matrix cores, NCHW)
 //   - rmsnorm_bf16 / rope_decode_bf16 / rope_scatter_decode_bf16 /
 //     decode_gemm_bf16 / sample_logits_bf16 (LLM decode step)
-//     fp8w_decode_gemm_bf16 / fp8w_dequant_bf16 (fp8 weight-only linears)
+//     fp8w_decode_gemm_bf16 / fp8w_gemm_bf16 + fp8w_gemm_tile /
+//     fp8w_dequant_bf16 (fp8 weight-only linears)
 //     mxfp4w_decode_gemm_bf16 / mxfp4w_dequant_bf16 (MXFP4 weight-only
 //     linears)
 //   - rope_scatter_decode_fp8kv_bf16 (the same scatter into an e4m3 KV
@@ -368,6 +369,14 @@ static void fp8w_decode_gemm_bf16(uintptr_t x, uintptr_t codes,
       reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
+static void fp8w_gemm_bf16(uintptr_t x, uintptr_t codes, uintptr_t scale_exp,
+                           uintptr_t y, int m, int n, int k,
+                           uintptr_t stream_handle) {
+  HIP_CHECK(ca_fp8w_gemm_bf16(
+      cptr(x), cptr(codes), cptr(scale_exp), mptr(y), m, n, k,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
 static void fp8w_dequant_bf16(uintptr_t codes, uintptr_t scale_exp,
                               uintptr_t w_out, int n, int k,
                               uintptr_t stream_handle) {
@@ -622,6 +631,10 @@ PYBIND11_MODULE(_hip_c, m) {
   m.def("fp8w_decode_gemm_bf16", &fp8w_decode_gemm_bf16, py::arg("x"),
         py::arg("codes"), py::arg("scale_exp"), py::arg("y"), py::arg("m"),
         py::arg("n"), py::arg("k"), py::arg("stream_handle"));
+  m.def("fp8w_gemm_bf16", &fp8w_gemm_bf16, py::arg("x"), py::arg("codes"),
+        py::arg("scale_exp"), py::arg("y"), py::arg("m"), py::arg("n"),
+        py::arg("k"), py::arg("stream_handle"));
+  m.def("fp8w_gemm_tile", &ca_fp8w_gemm_tile, py::arg("m"), py::arg("n"));
   m.def("fp8w_dequant_bf16", &fp8w_dequant_bf16, py::arg("codes"),
         py::arg("scale_exp"), py::arg("w_out"), py::arg("n"), py::arg("k"),
         py::arg("stream_handle"));

@@ -32,8 +32,36 @@
 // sums which chunk, and the number of waves, depend on (N, K) alone:
 // a row's output bits depend neither on M nor on the other rows.
 //
+// ca_fp8w_gemm_bf16: the same y for any M >= 1 (prefill chunks, decode
+// batches above 16 rows), a design of its own. A workgroup of 2 x 2 waves
+// owns a BM x BN tile of y with the whole K, BM = BN = 128, 64 or 32
+// chosen on the host from (M, N) alone (fg_tile_for); a wave owns a
+// quarter as WT x WT MFMA tiles (WT = 4, 2, 1). There is no K split: every
+// accumulator sees the 64-wide chunks in ascending order, both MFMA steps
+// of a chunk in order, and every variant runs the same MFMA shape. So a
+// row's output bits depend only on that row of x, on (N, K) and on the
+// weights: not on M, on the other rows or on the tile variant. They are
+// not the decode kernel's bits, which sums in another order.
+// Codes go global -> VGPR, one 16-byte lane load per 16-row tile and
+// chunk, no LDS, converted once per chunk and used against the wave's WT
+// column tiles. The BM x 64 chunk of x is staged through LDS, double
+// buffered, and read back as B fragments by the two waves that share the
+// rows. LDS rows are padded from 128 to 144 bytes: the 16 rows of a
+// fragment read then start 36 dwords apart and cover all 64 banks once
+// (unpadded they would start on the same bank). The loads of chunk c + 1
+// (codes to registers, x to registers on its way to the other buffer) are
+// issued unconditionally before chunk c is converted and multiplied; the
+// last chunk is a separate tail. One barrier per chunk. The epilogue
+// scales by 2^scale_exp[n], rounds RNE and stores straight from the D
+// fragment, whose lane holds four consecutive n of one row of y: 8-byte
+// stores (2-byte ones where N % 4 != 0), 32 WT contiguous bytes per row
+// and wave. A pass through LDS for 16-byte stores was not tried.
+// -Rpass-analysis=kernel-resource-usage, gfx950, tile 128 / 64 / 32:
+// 124 / 59 / 44 VGPRs + 96 / 24 / 4 AGPRs, LDS 36864 / 18432 / 9216 bytes,
+// scratch 0 / 0 / 0, occupancy 2 / 5 / 8 waves per SIMD.
+//
 // ca_fp8w_dequant_bf16: packed codes -> the bf16 bits of W_eff, row-major
-// [N, K]; for the prefill route, which runs the library GEMM on it.
+// [N, K]; for the dequant route, which runs the library GEMM on it.
 
 #define FW_ROWS 16      // output channels per tile (MFMA A rows)
 #define FW_KCHUNK 64    // k per tile: 64 lanes x 16 B / 16 rows
@@ -222,7 +250,193 @@ fp8w_dequant_kernel(const uint8_t* __restrict__ packed,
   }
 }
 
+// ---------------------------------------------------------------------------
+// wide GEMM (M > 16: prefill chunks, wide decode batches)
+// ---------------------------------------------------------------------------
+
+#define FG_THREADS 256  // 2 x 2 waves
+#define FG_ROW_U4 9     // an LDS row of x: 8 x 16 B of data and 16 B of pad
+#define FG_MIN_BLOCKS 192
+
 namespace {
+
+// The format-specific part of the wide kernel: one 16-byte lane load per
+// 16-row tile and chunk, and the A fragment of MFMA step s from it.
+__device__ __forceinline__ fw_u32x4 fg_load_codes(const fw_u32x4* p) {
+  return *p;
+}
+
+__device__ __forceinline__ fw_frag_ab fg_codes_to_frag(const fw_u32x4& w,
+                                                       int s) {
+  return s == 0 ? fw_codes8_to_frag(w.x, w.y) : fw_codes8_to_frag(w.z, w.w);
+}
+
+// One 64-wide chunk for a wave's WT x WT MFMA tiles: per step WT B
+// fragments from LDS (sx points at the wave's row r, 16-byte piece 2 q),
+// WT A fragments converted once and used against all of them.
+template <int WT>
+__device__ __forceinline__ void fg_chunk(const fw_u32x4* sx,
+                                         const fw_u32x4 (&w)[WT],
+                                         fw_frag_cd (&acc)[WT][WT]) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    fw_frag_u b[WT];
+#pragma unroll
+    for (int i = 0; i < WT; ++i) b[i].u = sx[16 * i * FG_ROW_U4 + s];
+#pragma unroll
+    for (int j = 0; j < WT; ++j) {
+      const fw_frag_ab a = fg_codes_to_frag(w[j], s);
+#pragma unroll
+      for (int i = 0; i < WT; ++i)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b[i].f,
+                                                            acc[i][j], 0, 0, 0);
+    }
+  }
+}
+
+}  // namespace
+
+// A workgroup owns the (32 WT) x (32 WT) tile (mb, nb) of y with the whole
+// K; wave (wave >> 1, wave & 1) owns its (16 WT) x (16 WT) quarter as
+// WT x WT MFMA tiles, weights as A (rows n), x as B (columns m).
+template <int WT>
+__global__ void __launch_bounds__(FG_THREADS)
+fp8w_gemm_kernel(const uint16_t* __restrict__ x,
+                 const uint8_t* __restrict__ packed,
+                 const int8_t* __restrict__ scale_exp,
+                 uint16_t* __restrict__ y, int M, int N, int K, int mblocks) {
+  constexpr int BT = 32 * WT;
+  __shared__ fw_u32x4 s_x[2][BT * FG_ROW_U4];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int r = lane & 15;
+  const int q = lane >> 4;
+  // the row blocks of one column block are neighbours in launch order:
+  // they read the same codes
+  const int m0 = (int)(blockIdx.x % mblocks) * BT;
+  const int n0 = (int)(blockIdx.x / mblocks) * BT;
+  const int wm0 = (wave >> 1) * 16 * WT;
+  const int wn0 = (wave & 1) * 16 * WT;
+  const int kc = K / FW_KCHUNK;
+  const int tiles = (N + FW_ROWS - 1) / FW_ROWS;
+
+  // staging of x: the BT x 128 B chunk is BT x 8 pieces of 16 B, WT per
+  // thread, 8 consecutive threads one row. Rows >= M repeat row M - 1:
+  // they feed only outputs nobody writes, and x is never read beyond its
+  // last row.
+  const fw_u32x4* xg[WT];
+  int xs[WT];
+#pragma unroll
+  for (int i = 0; i < WT; ++i) {
+    const int p = tid + FG_THREADS * i;
+    const int row = p >> 3;
+    const int gm = m0 + row < M ? m0 + row : M - 1;
+    xg[i] = reinterpret_cast<const fw_u32x4*>(x + (long)gm * K) + (p & 7);
+    xs[i] = row * FG_ROW_U4 + (p & 7);
+  }
+  // codes: 16-row tiles beyond the padded N repeat the last one, for the
+  // same reason
+  const fw_u32x4* wg[WT];
+#pragma unroll
+  for (int j = 0; j < WT; ++j) {
+    int t = (n0 + wn0) / FW_ROWS + j;
+    t = t < tiles ? t : tiles - 1;
+    wg[j] = reinterpret_cast<const fw_u32x4*>(packed) + (long)t * kc * 64 +
+            lane;
+  }
+
+  fw_frag_cd acc[WT][WT];
+#pragma unroll
+  for (int i = 0; i < WT; ++i)
+#pragma unroll
+    for (int j = 0; j < WT; ++j) acc[i][j] = fw_frag_cd{0.f, 0.f, 0.f, 0.f};
+
+  fw_u32x4 w[WT], xr[WT];
+#pragma unroll
+  for (int j = 0; j < WT; ++j) w[j] = fg_load_codes(wg[j]);
+#pragma unroll
+  for (int i = 0; i < WT; ++i) xr[i] = xg[i][0];
+#pragma unroll
+  for (int i = 0; i < WT; ++i) s_x[0][xs[i]] = xr[i];
+  __syncthreads();
+
+  // lane (m = r, q) reads x[m][64 c + 16 q + 8 s ...] at step s, the k of
+  // the weight lane (r, q)'s bytes 8 s ...
+  const int sx0 = (wm0 + r) * FG_ROW_U4 + 2 * q;
+  // steady state: the loads of chunk c + 1 (codes to registers, x to
+  // registers on its way to the other LDS buffer) are issued, without a
+  // condition, before chunk c is converted and multiplied. One barrier
+  // per chunk: the buffer written here was last read before the previous
+  // barrier.
+  int c = 0;
+  for (; c + 1 < kc; ++c) {
+    fw_u32x4 wn[WT];
+#pragma unroll
+    for (int j = 0; j < WT; ++j)
+      wn[j] = fg_load_codes(wg[j] + (long)(c + 1) * 64);
+#pragma unroll
+    for (int i = 0; i < WT; ++i) xr[i] = xg[i][(long)(c + 1) * 8];
+    __builtin_amdgcn_sched_barrier(0);
+    fg_chunk<WT>(&s_x[c & 1][sx0], w, acc);
+#pragma unroll
+    for (int i = 0; i < WT; ++i) s_x[(c + 1) & 1][xs[i]] = xr[i];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < WT; ++j) w[j] = wn[j];
+  }
+  // tail: the last chunk, nothing left to load
+  fg_chunk<WT>(&s_x[c & 1][sx0], w, acc);
+
+  // D[n = 4 q + e][m = r] in acc[i][j][e]: a lane holds four consecutive n
+  // of one row of y, the four q of a row 32 contiguous bytes, the WT
+  // tiles of a wave 32 WT. 8-byte stores where y's rows allow them.
+  const bool vec = (N & 3) == 0 && ((uintptr_t)y & 7) == 0;
+#pragma unroll
+  for (int j = 0; j < WT; ++j) {
+    const int n = n0 + wn0 + 16 * j + 4 * q;
+    float sc[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      sc[e] = fw_exp2i(scale_exp[n + e < N ? n + e : N - 1]);
+#pragma unroll
+    for (int i = 0; i < WT; ++i) {
+      const int m = m0 + wm0 + 16 * i + r;
+      if (m >= M) continue;
+      uint16_t o[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        o[e] = __bfloat16_as_ushort(__float2bfloat16(acc[i][j][e] * sc[e]));
+      uint16_t* dst = y + (long)m * N + n;
+      if (vec && n + 3 < N) {
+        *reinterpret_cast<uint2*>(dst) =
+            uint2{(uint32_t)o[0] | ((uint32_t)o[1] << 16),
+                  (uint32_t)o[2] | ((uint32_t)o[3] << 16)};
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (n + e < N) dst[e] = o[e];
+      }
+    }
+  }
+}
+
+namespace {
+
+// Tile edge of the wide GEMM (BM = BN = 128, 64 or 32), from (M, N)
+// alone: the largest whose grid has at least FG_MIN_BLOCKS workgroups,
+// about one per CU of the 256; 32 where none has. Larger tiles re-read x
+// and the codes less often (each N / BN and M / BM times), smaller ones
+// fill the CUs; every variant runs the same MFMAs in the same k order.
+inline long fg_blocks(int M, int N, int t) {
+  return (((long)M + t - 1) / t) * (((long)N + t - 1) / t);
+}
+
+inline int fg_tile_for(int M, int N) {
+  for (int t = 128; t > 32; t /= 2)
+    if (fg_blocks(M, N, t) >= FG_MIN_BLOCKS) return t;
+  return 32;
+}
 
 // waves per workgroup, from the shape alone: fewer waves where there are
 // enough tiles to fill the CUs several times over, never more than
@@ -263,6 +477,42 @@ extern "C" hipError_t ca_fp8w_decode_gemm_bf16(const void* x,
     default: FW_LAUNCH(16); break;
   }
 #undef FW_LAUNCH
+  return hipGetLastError();
+}
+
+// The tile edge ca_fp8w_gemm_bf16 uses for (M, N); 0 outside its contract.
+extern "C" int ca_fp8w_gemm_tile(int M, int N) {
+  return M < 1 || N < 1 ? 0 : fg_tile_for(M, N);
+}
+
+// The decode GEMM's semantics without its limit on M: x [M, K] bf16,
+// packed codes of W[N, K], scale_exp [N] int8, y [M, N] bf16. M >= 1,
+// N >= 1, K % 64 == 0; x and packed 16-byte aligned, y 2-byte aligned.
+// Anything else returns hipErrorInvalidValue before any launch. No
+// workspace, no atomics.
+extern "C" hipError_t ca_fp8w_gemm_bf16(const void* x, const void* codes,
+                                        const void* scale_exp, void* y, int M,
+                                        int N, int K, hipStream_t stream) {
+  if (M < 1 || N < 1 || K < FW_KCHUNK || K % FW_KCHUNK != 0)
+    return hipErrorInvalidValue;
+  if (!x || !codes || !scale_exp || !y) return hipErrorInvalidValue;
+  if (((uintptr_t)x | (uintptr_t)codes) % 16 != 0 || (uintptr_t)y % 2 != 0)
+    return hipErrorInvalidValue;
+  const int tile = fg_tile_for(M, N);
+  const long blocks = fg_blocks(M, N, tile);
+  if (blocks > 0x7FFFFFFFL) return hipErrorInvalidValue;
+  const int mblocks = (int)(((long)M + tile - 1) / tile);
+#define FG_LAUNCH(WT)                                                       \
+  hipLaunchKernelGGL((fp8w_gemm_kernel<WT>), dim3((uint32_t)blocks),         \
+                     dim3(FG_THREADS), 0, stream, (const uint16_t*)x,       \
+                     (const uint8_t*)codes, (const int8_t*)scale_exp,       \
+                     (uint16_t*)y, M, N, K, mblocks)
+  switch (tile) {
+    case 128: FG_LAUNCH(4); break;
+    case 64: FG_LAUNCH(2); break;
+    default: FG_LAUNCH(1); break;
+  }
+#undef FG_LAUNCH
   return hipGetLastError();
 }
 

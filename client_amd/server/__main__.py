@@ -15,7 +15,8 @@ import threading
 def build_core(model_names, device="cuda:0", dtype="bf16",
                decode_max_batch=8, prewarm_sampling=False,
                kv_cache_dtype=None, fused_prefill=False,
-               weight_dtype=None, bert_fused_attention=False):
+               weight_dtype=None, bert_fused_attention=False,
+               fp8_weight_gemm=False):
     from . import (
         AddSubModel,
         IdentityModel,
@@ -25,6 +26,8 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
         TorchModel,
     )
 
+    if fp8_weight_gemm and weight_dtype != "fp8_e4m3":
+        raise SystemExit("--fp8-weight-gemm needs --weight-dtype fp8_e4m3")
     core = InferenceCore()
     for name in model_names:
         if name == "identity_fp32":
@@ -131,7 +134,8 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
                               prewarm_sampling=prewarm_sampling,
                               kv_cache_dtype=kv_cache_dtype,
                               fused_prefill=fused_prefill,
-                              weight_dtype=weight_dtype)
+                              weight_dtype=weight_dtype,
+                              fp8_weight_gemm=fp8_weight_gemm)
             )
         elif name == "ensemble_image":
             # preprocess (HIP kernel on GPU) -> resnet50 pipeline; the
@@ -214,6 +218,12 @@ def build_parser():
                              "mxfp4 as e2m1 codes with a power-of-two scale "
                              "per 32 elements (0.53 bytes per weight) read "
                              "by the MXFP4-weight decode GEMM kernel")
+    parser.add_argument("--fp8-weight-gemm", action="store_true",
+                        help="with --weight-dtype fp8_e4m3: run linear "
+                             "calls of more than 16 rows (prefill chunks, "
+                             "decode steps of more than 16 slots) on the "
+                             "fp8-weight MFMA GEMM kernel instead of "
+                             "dequantising the layer for the library GEMM")
     parser.add_argument("--fused-prefill", action="store_true",
                         help="run the prefill chunks of generate models on "
                              "the fused RoPE + scatter and MFMA attention "
@@ -246,6 +256,7 @@ def main(argv=None):
         fused_prefill=args.fused_prefill,
         weight_dtype=args.weight_dtype,
         bert_fused_attention=args.bert_fused_attention,
+        fp8_weight_gemm=args.fp8_weight_gemm,
     )
     if args.dynamic_batching:
         for model in core.models.values():

@@ -275,12 +275,18 @@ class GenerateModel(Model):
 
     ``fused_prefill`` sets the module's ``fused_prefill`` (prefill chunks
     on the fused HIP kernels, models/llama.py); the served config then
-    carries a ``fused_prefill`` parameter."""
+    carries a ``fused_prefill`` parameter.
+
+    ``fp8_weight_gemm`` (only with ``weight_dtype`` "fp8_e4m3", otherwise
+    ValueError) runs the e4m3 layers' calls of more than 16 rows, prefill
+    chunks and wide decode steps, on the fp8-weight MFMA GEMM instead of
+    the dequant route; the served config then carries an
+    ``fp8_weight_gemm`` parameter."""
 
     def __init__(self, name, llama_module, device="cuda:0", dtype=None,
                  use_scheduler=True, max_batch=8, prewarm_sampling=False,
                  kv_cache_dtype=None, fused_prefill=False,
-                 weight_dtype=None):
+                 weight_dtype=None, fp8_weight_gemm=False):
         super().__init__(
             name,
             [("input_ids", "INT64", [-1]), ("max_tokens", "INT32", [1]),
@@ -304,8 +310,13 @@ class GenerateModel(Model):
             self.module = self.module.to(dtype)
         self.module.eval()
         self.weight_dtype = normalize_weight_dtype(weight_dtype)
+        self.fp8_weight_gemm = bool(fp8_weight_gemm)
+        if self.fp8_weight_gemm and self.weight_dtype != "fp8_e4m3":
+            raise ValueError("fp8_weight_gemm needs weight_dtype "
+                             f"'fp8_e4m3', not {weight_dtype!r}")
         if self.weight_dtype is not None:
-            quantize_llama_weights_as(self.module, self.weight_dtype)
+            quantize_llama_weights_as(self.module, self.weight_dtype,
+                                      fused_gemm=self.fp8_weight_gemm)
         self.fused_prefill = bool(fused_prefill)
         if self.fused_prefill:
             self.module.fused_prefill = True
@@ -332,6 +343,8 @@ class GenerateModel(Model):
             params["kv_cache_dtype"] = {"string_value": self.kv_cache_dtype}
         if self.weight_dtype is not None:
             params["weight_dtype"] = {"string_value": self.weight_dtype}
+        if self.fp8_weight_gemm:
+            params["fp8_weight_gemm"] = {"string_value": "true"}
         if self.fused_prefill:
             params["fused_prefill"] = {"string_value": "true"}
         if params:

@@ -13,6 +13,10 @@ replay) / copies, the two variants alternating within a round. Achieved
 bytes/s counts the bytes the algorithm needs: N K for fp8, 2 N K for
 bf16.
 
+Wide GEMM (--wide, nothing else then runs): the same method at M = 24 to
+1024 for fp8w_gemm_bf16, the dequant route (fp8w_dequant_bf16 into the
+shared scratch + F.linear) and F.linear on bf16 weights.
+
 Memory: torch.cuda.memory_allocated() before and after
 quantize_llama_weights on the 8B model (--memory).
 
@@ -35,6 +39,8 @@ M = 8
 SHAPES = [(4096, 4096), (1024, 4096), (14336, 4096), (4096, 14336)]
 WALK_BYTES = 512 << 20
 PEAK_BYTES_PER_S = 6.3e12  # achievable HBM read rate, MI355X_MICROARCH.md
+WIDE_M = (24, 64, 128, 512, 1024)
+PEAK_BF16_FLOPS = 2.5e15  # dense bf16 MFMA roof, MI355X_MICROARCH.md
 
 
 def _capture(torch, fn):
@@ -118,6 +124,89 @@ def bench_kernel(torch, n, k, rounds, iters):
     return out
 
 
+def bench_wide(torch, n, k, rounds, iters):
+    """--wide: M > 16 on fp8w_gemm_bf16, on the dequant route (what
+    Fp8Linear runs without fused_gemm) and on F.linear with bf16 weights
+    of the same values; the method of bench_kernel. The bound of a call
+    is the larger of 2 M N K FLOPs at the bf16 MFMA roof and the bytes
+    the algorithm needs (codes or bf16 weights once, x once, y once) at
+    the HBM read rate."""
+    import torch.nn.functional as F
+
+    from client_amd.models.weight_fp8 import Fp8Linear, quantize_weight
+    from client_amd.ops import hip_runtime as hr
+
+    dev = "cuda:0"
+    g = torch.Generator(device=dev).manual_seed(n + k)
+    copies8 = WALK_BYTES // (n * k) + 1
+    copies16 = WALK_BYTES // (2 * n * k) + 1
+    w0 = torch.randn(n, k, device=dev, generator=g) * k ** -0.5
+    lin0 = Fp8Linear(*quantize_weight(w0)).to(dev)
+    fp8 = [lin0] + [copy.deepcopy(lin0) for _ in range(copies8 - 1)]
+    for lin in fp8:  # one dequant scratch for all, as in a model
+        lin._scratch = lin0._scratch
+    w_eff = lin0.effective_weight(torch.bfloat16)
+    bf16 = [w_eff] + [w_eff.clone() for _ in range(copies16 - 1)]
+    rows = []
+    for m in WIDE_M:
+        x = torch.randn(m, k, device=dev, generator=g).to(torch.bfloat16)
+
+        def run_fp8(fused):
+            for lin in fp8:
+                lin.fused_gemm = fused
+                lin(x)
+
+        def run_bf16():
+            for w in bf16:
+                F.linear(x, w)
+
+        lin0.fused_gemm = True
+        max_diff = float((lin0(x).float() - F.linear(x, w_eff).float())
+                         .abs().max())
+        # the route is fixed when the step is captured
+        variants = {
+            "fp8_gemm": (_capture(torch, lambda: run_fp8(True)), copies8, 1),
+            "dequant_route": (_capture(torch, lambda: run_fp8(False)),
+                              copies8, 1),
+            "bf16_library": (_capture(torch, run_bf16), copies16, 2)}
+        for fn, _, _ in variants.values():
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        times = {name: [] for name in variants}
+        for _ in range(rounds):
+            for name, (fn, copies, _) in variants.items():
+                times[name].append(_time_step(torch, fn, iters) / copies)
+        flops = 2 * m * n * k
+        out = {"M": m, "N": n, "K": k, "tile": hr.fp8w_gemm_tile(m, n),
+               "fp8_gemm_vs_bf16_max_abs_diff": max_diff}
+        for name, ts in times.items():
+            _, copies, elem = variants[name]
+            need = n * k * elem + 2 * m * k + 2 * m * n
+            t_flops = flops / PEAK_BF16_FLOPS
+            t_bytes = need / PEAK_BYTES_PER_S
+            us = statistics.median(ts)
+            out[name] = {
+                "copies_per_step": copies,
+                "us_per_call": round(us, 2),
+                "us_min": round(min(ts), 2), "us_max": round(max(ts), 2),
+                "TFLOP_per_s": round(flops / us / 1e6, 1),
+                "needed_bytes": need,
+                "bound": "flops" if t_flops > t_bytes else "bytes",
+                "share_of_bound": round(max(t_flops, t_bytes) / (us * 1e-6),
+                                        3),
+            }
+        out["fp8_gemm_over_dequant_time"] = round(
+            out["fp8_gemm"]["us_per_call"]
+            / out["dequant_route"]["us_per_call"], 3)
+        out["fp8_gemm_over_bf16_time"] = round(
+            out["fp8_gemm"]["us_per_call"]
+            / out["bf16_library"]["us_per_call"], 3)
+        rows.append(out)
+        print(json.dumps(out), flush=True)
+    return rows
+
+
 def _decode_logits(torch, model, prompt, steps):
     dev = prompt.device
     kv = model.make_kv_cache(1, dev, torch.bfloat16)
@@ -181,6 +270,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--skip-drift", action="store_true")
+    ap.add_argument("--wide", action="store_true",
+                    help="only the M > 16 section: fp8w_gemm_bf16 against "
+                         "the dequant route and the bf16 library GEMM")
     ap.add_argument("--memory", action="store_true",
                     help="also build and quantise the 8B model")
     args = ap.parse_args()
@@ -192,6 +284,16 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("needs a HIP device: a CPU run gives no timing")
+    if args.wide:
+        report = {"wide": []}
+        with torch.inference_mode():
+            for n, k in SHAPES:
+                report["wide"] += bench_wide(torch, n, k, args.rounds,
+                                             args.iters)
+                torch.cuda.empty_cache()
+        with open(args.json, "w") as f:
+            json.dump(report, f, indent=1)
+        return
     report = {"kernel": [], "drift": {}, "memory": None}
     with torch.inference_mode():
         for n, k in SHAPES:
