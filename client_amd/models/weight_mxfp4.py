@@ -175,10 +175,17 @@ class Mxfp4Linear(nn.Module):
     Fp8Linear: the MFMA decode GEMM (mxfp4w_decode_gemm_bf16) for bf16 x
     of 1..16 rows on a HIP device; mxfp4w_dequant_bf16 into the shared
     bf16 scratch plus F.linear for any other x on a HIP device; F.linear
-    on effective_weight on the CPU."""
+    on effective_weight on the CPU.
 
-    def __init__(self, codes, scales, scratch=None):
+    ``wide_gemm`` (default False) adds a fourth: bf16 x of more than 16
+    rows on a HIP device runs the tiled MFMA GEMM (mxfp4w_gemm_bf16) on
+    the same two buffers, which reads the codes straight into registers
+    and stages x through LDS. With it set, no bf16 call with a contiguous,
+    16-byte-aligned x touches the scratch."""
+
+    def __init__(self, codes, scales, scratch=None, wide_gemm=False):
         super().__init__()
+        self.wide_gemm = bool(wide_gemm)
         n, half = codes.shape
         self.in_features = 2 * half
         self.out_features = n
@@ -234,18 +241,20 @@ class Mxfp4Linear(nn.Module):
         if not x.is_cuda:
             return F.linear(x, self.effective_weight(x.dtype))
         m = x.numel() // k
-        if x.dtype == torch.bfloat16 and 1 <= m <= MAX_DECODE_M:
+        if x.dtype == torch.bfloat16 and (
+                1 <= m <= MAX_DECODE_M or (self.wide_gemm and m >= 1)):
             x2 = x.reshape(m, k).contiguous()
-            # the kernel's one requirement that a view of x can miss; any
-            # error it raises beyond that is a real one and propagates
+            # the kernels' one requirement that a view of x can miss; any
+            # error they raise beyond that is a real one and propagates
             if x2.data_ptr() % 16 == 0:
                 from ..ops import hip_runtime as hr
 
+                gemm = (hr.mxfp4w_decode_gemm_bf16 if m <= MAX_DECODE_M
+                        else hr.mxfp4w_gemm_bf16)
                 y = torch.empty(m, n, device=x.device, dtype=torch.bfloat16)
-                hr.mxfp4w_decode_gemm_bf16(
-                    x2.data_ptr(), self.codes.data_ptr(),
-                    self.scales.data_ptr(), y.data_ptr(), m, n, k,
-                    torch.cuda.current_stream().cuda_stream)
+                gemm(x2.data_ptr(), self.codes.data_ptr(),
+                     self.scales.data_ptr(), y.data_ptr(), m, n, k,
+                     torch.cuda.current_stream().cuda_stream)
                 return y.view(*x.shape[:-1], n)
         w = self.dequant_to_scratch()
         if w.dtype != x.dtype:
@@ -256,16 +265,26 @@ class Mxfp4Linear(nn.Module):
 LAYER_CLASSES = {"fp8_e4m3": Fp8Linear, "mxfp4": Mxfp4Linear}
 
 
-def quantize_llama_weights_as(model, weight_dtype, fused_gemm=False):
+def quantize_llama_weights_as(model, weight_dtype, fused_gemm=False,
+                              wide_gemm=False):
     """quantize_llama_weights with the layer class of ``weight_dtype``
     ("fp8_e4m3" or "mxfp4"). ``fused_gemm`` (the wide fp8 GEMM for
-    M > 16) exists for "fp8_e4m3" only."""
+    M > 16) exists for "fp8_e4m3" only, ``wide_gemm`` (the wide MXFP4
+    GEMM, Mxfp4Linear.wide_gemm on every created layer) for "mxfp4" only."""
     if fused_gemm and weight_dtype != "fp8_e4m3":
         raise ValueError(f"fused_gemm needs weight_dtype 'fp8_e4m3', not "
                          f"{weight_dtype!r}")
-    return quantize_llama_weights(model,
-                                  layer_cls=LAYER_CLASSES[weight_dtype],
-                                  fused_gemm=fused_gemm)
+    if wide_gemm and weight_dtype != "mxfp4":
+        raise ValueError(f"wide_gemm needs weight_dtype 'mxfp4', not "
+                         f"{weight_dtype!r}")
+    stats = quantize_llama_weights(model,
+                                   layer_cls=LAYER_CLASSES[weight_dtype],
+                                   fused_gemm=fused_gemm)
+    if wide_gemm:
+        for mod in model.modules():
+            if isinstance(mod, Mxfp4Linear):
+                mod.wide_gemm = True
+    return stats
 
 
 __all__ = ["WEIGHT_DTYPES", "LLAMA_BLOCK_LINEARS", "LAYER_CLASSES",

@@ -24,8 +24,8 @@
 //     decode_gemm_bf16 / sample_logits_bf16 (LLM decode step)
 //     fp8w_decode_gemm_bf16 / fp8w_gemm_bf16 + fp8w_gemm_tile /
 //     fp8w_dequant_bf16 (fp8 weight-only linears)
-//     mxfp4w_decode_gemm_bf16 / mxfp4w_dequant_bf16 (MXFP4 weight-only
-//     linears)
+//     mxfp4w_decode_gemm_bf16 / mxfp4w_gemm_bf16 + mxfp4w_gemm_tile /
+//     mxfp4w_dequant_bf16 (MXFP4 weight-only linears)
 //   - rope_scatter_decode_fp8kv_bf16 (the same scatter into an e4m3 KV
 //     cache) / gqa_decode_attention + gqa_decode_attention_workspace_bytes
 //     (fused split + combine decode attention over a bf16 or e4m3 cache;
@@ -393,6 +393,14 @@ static void mxfp4w_decode_gemm_bf16(uintptr_t x, uintptr_t codes,
       reinterpret_cast<hipStream_t>(stream_handle)));
 }
 
+static void mxfp4w_gemm_bf16(uintptr_t x, uintptr_t codes, uintptr_t scales,
+                             uintptr_t y, int m, int n, int k,
+                             uintptr_t stream_handle) {
+  HIP_CHECK(ca_mxfp4w_gemm_bf16(
+      cptr(x), cptr(codes), cptr(scales), mptr(y), m, n, k,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
 static void mxfp4w_dequant_bf16(uintptr_t codes, uintptr_t scales,
                                 uintptr_t w_out, int n, int k,
                                 uintptr_t stream_handle) {
@@ -644,6 +652,10 @@ PYBIND11_MODULE(_hip_c, m) {
   m.def("mxfp4w_decode_gemm_bf16", &mxfp4w_decode_gemm_bf16, py::arg("x"),
         py::arg("codes"), py::arg("scales"), py::arg("y"), py::arg("m"),
         py::arg("n"), py::arg("k"), py::arg("stream_handle"));
+  m.def("mxfp4w_gemm_bf16", &mxfp4w_gemm_bf16, py::arg("x"),
+        py::arg("codes"), py::arg("scales"), py::arg("y"), py::arg("m"),
+        py::arg("n"), py::arg("k"), py::arg("stream_handle"));
+  m.def("mxfp4w_gemm_tile", &ca_mxfp4w_gemm_tile, py::arg("m"), py::arg("n"));
   m.def("mxfp4w_dequant_bf16", &mxfp4w_dequant_bf16, py::arg("codes"),
         py::arg("scales"), py::arg("w_out"), py::arg("n"), py::arg("k"),
         py::arg("stream_handle"));

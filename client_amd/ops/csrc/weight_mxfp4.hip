@@ -55,6 +55,10 @@
 // number of waves and which wave sums which chunk depend on (N, K)
 // alone: a row's output bits depend neither on M nor on other rows.
 //
+// ca_mxfp4w_gemm_bf16: the same y for any M >= 1 (prefill chunks, decode
+// steps above 16 rows), a design of its own; see the comment in front of
+// mxfp4w_gemm_kernel.
+//
 // ca_mxfp4w_dequant_bf16: the packed layout -> the bf16 bits of W_eff,
 // row-major [N, K], for the route that runs the library GEMM.
 
@@ -83,6 +87,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 fm_frag_ab;
 typedef __attribute__((ext_vector_type(2))) __bf16 fm_bf16x2;
 typedef __attribute__((ext_vector_type(4))) float fm_frag_cd;
 typedef __attribute__((ext_vector_type(4))) uint32_t fm_u32x4;
+typedef __attribute__((ext_vector_type(2))) uint32_t fm_u32x2;
 
 union fm_frag_u {
   fm_u32x4 u;
@@ -272,6 +277,262 @@ mxfp4w_decode_gemm_kernel(const uint16_t* __restrict__ x,
   }
 }
 
+// The wide GEMM: y[M, N] = bf16_rne(sum_k x[m, k] W_eff[n, k]), any M >= 1.
+//
+// Split. A workgroup of WAVES waves owns a BN x BM tile of y with the
+// whole K, BN = 64 WAVES output channels by BM = 16 MT rows of x. A wave
+// owns one whole 64-row group of W (four 16-row code tiles, whose four
+// scale bytes arrive in one dword per lane and chunk) against all MT
+// 16-row tiles of x: 4 x MT accumulators. The waves of a workgroup split N
+// only, so all of them read the same x. Three variants, BN x BM =
+// 64 x 32 (1 wave), 128 x 64 (2) and 256 x 128 (4), picked on the host
+// from (M, N) alone (fmg_tile_for).
+//
+// Operands. Codes go global -> VGPR, never through LDS: per chunk a lane
+// loads one MX block (16 B) of row r of each of the four tiles. A dword
+// of it becomes an A fragment by four v_cvt_scalef32_pk_bf16_fp4 with the
+// scale s << 23 (nothing is left for the epilogue) and is multiplied
+// against all MT x tiles before the next dword is converted. x is the B
+// operand: the BM x 128 chunk goes global -> registers -> LDS (8 pieces of
+// 16 B per thread in every variant) and is read back once per chunk and
+// wave, step by step, as MT fragments of 16 B per lane at
+// k = 128 c + 32 q + 8 s, the k of dword s of the weight lane (r, q)'s
+// block: the same permutation on both operands as in the decode kernel.
+// LDS rows are padded from 256 to 272 bytes: the 16 rows of a fragment
+// read start 68 dwords apart, 4 r mod 64, and cover the 64 banks once.
+//
+// Pipeline. Two LDS buffers for x, three register stages for the codes.
+// Step c writes x of chunk c + 1 (loaded one step ago) to the buffer that
+// chunk c - 1 was read from, issues the loads of chunk c + 2 (x, then the
+// codes and scales), converts and multiplies chunk c, whose codes were
+// loaded two steps ago, and ends in the chunk's one barrier. Every load
+// of the steady loop is unconditional (a ragged last chunk is a select on
+// the address and a mask, not a branch). The steady loop is three steps
+// long so that the stages rotate by name: rotating them by register moves
+// made every move wait for the load just issued (vmcnt(1) at the loop
+// top). At most two more steps, which do rotate by moves, and the last
+// two chunks are a separate tail. In the steady loop's assembly (all
+// three variants) the only vmcnt waits are those of the eight LDS writes:
+// vmcnt(12) .. vmcnt(5) in the step that writes before it loads,
+// vmcnt(25) .. vmcnt(18) in the two where the compiler moved the 13 loads
+// of chunk c + 2 in front of the writes. Either way the 5 code and scale
+// loads of chunk c + 1 and all 13 loads of chunk c + 2 stay in flight
+// across the converts, the MFMAs and the barrier, which has no vmcnt wait
+// in front of it. x of chunk c + 1 is waited for one step after its
+// issue, so a step cannot be shorter than one memory latency; a second
+// register stage for x would lift that and is not done here.
+//
+// Order of summation. No K split, no atomics, no workspace: every
+// accumulator sees the chunks in ascending order and the four MFMA steps
+// of a chunk in order, in every variant. A row's output bits depend on
+// that row of x, on (N, K) and on the weights only: not on M, on the
+// other rows or on the variant. They are not the decode kernel's bits,
+// whose waves split K.
+//
+// Edges. A 16-byte piece of x at k >= K (K % 32 == 0, so it is wholly in
+// or out) is read at the row's k = 0 instead and staged as zero bits.
+// Rows m >= M repeat row M - 1 and 64-row groups beyond the padded N
+// repeat the last one; neither is stored. Stores come straight from the D
+// fragment, four consecutive n of one y row per lane: 8-byte where
+// N % 4 == 0 and y is 8-byte aligned, else 2-byte.
+//
+// -Rpass-analysis=kernel-resource-usage, gfx950, 64x32 / 128x64 / 256x128:
+// 256 / 226 / 256 VGPRs + 56 / 108 / 228 AGPRs, LDS 17408 / 34816 / 69632
+// bytes, scratch 0 / 0 / 0, occupancy 1 / 1 / 1 wave per SIMD. (The
+// accumulators are 32 / 64 / 128 registers; the rest of the budget of a
+// one-wave-per-SIMD kernel went to renamed x stages and early converts.)
+#define FMG_ROW_U4 17  // 16-byte pieces per LDS row of x: 16 + 1 of padding
+
+namespace {
+
+// the codes and scales a lane loads for one chunk of its 64-row group
+struct fmg_stage {
+  fm_u32x4 w[4];    // one MX block of row r of each of the four tiles
+  uint32_t scales;  // byte i: the scale of w[i]
+};
+
+__device__ __forceinline__ void fmg_load_codes(fmg_stage& st,
+                                               const fm_u32x4* wg,
+                                               const uint32_t* sg, int c,
+                                               int kc) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    st.w[i] = __builtin_nontemporal_load(wg + ((long)i * kc + c) * 64);
+  st.scales = sg[(long)c * 64];
+}
+
+// member by member: a struct assignment copies the padding too and puts
+// the stages into scratch memory
+__device__ __forceinline__ void fmg_move(fmg_stage& to, const fmg_stage& from) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) to.w[i] = from.w[i];
+  to.scales = from.scales;
+}
+
+// chunk c of x: sx + FMG_ROW_U4 * (16 j + r) + 4 q + s is the fragment of
+// x tile j at step s
+template <int MT>
+__device__ __forceinline__ void fmg_compute(const fm_u32x4* sx,
+                                            const fmg_stage& st,
+                                            fm_frag_cd (&acc)[4][MT]) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    fm_frag_u b[MT];
+#pragma unroll
+    for (int j = 0; j < MT; ++j) b[j].u = sx[FMG_ROW_U4 * 16 * j + s];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      fm_frag_u a;
+      a.u = fm_codes8_to_bf16x8(st.w[i][s],
+                                ((st.scales >> (8 * i)) & 0xFFu) << 23);
+#pragma unroll
+      for (int j = 0; j < MT; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.f, b[j].f,
+                                                            acc[i][j], 0, 0, 0);
+    }
+  }
+}
+
+}  // namespace
+
+template <int WAVES, int MT>
+__global__ void FM_KERNEL_ATTR __launch_bounds__(WAVES * 64)
+mxfp4w_gemm_kernel(const uint16_t* __restrict__ x,
+                   const uint8_t* __restrict__ packed,
+                   const uint8_t* __restrict__ scales,
+                   uint16_t* __restrict__ y, int M, int N, int K,
+                   int mblocks) {
+  constexpr int THREADS = WAVES * 64;
+  constexpr int BM = 16 * MT;
+  constexpr int PX = BM * 16 / THREADS;  // 16-byte pieces of x per thread
+  static_assert(PX * THREADS == BM * 16, "x pieces must divide evenly");
+  __shared__ fm_u32x4 s_x[2][BM * FMG_ROW_U4];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int r = lane & 15;
+  const int q = lane >> 4;
+  const int kc = (K + FM_KCHUNK - 1) / FM_KCHUNK;
+  // the row blocks of one column block are neighbours in launch order:
+  // they read the same codes
+  const int m0 = (int)(blockIdx.x % mblocks) * BM;
+  const long group = (long)(blockIdx.x / mblocks) * WAVES + wave;
+  const long groups = ((long)N + FM_GROUP - 1) / FM_GROUP;
+  const long gc = group < groups ? group : groups - 1;
+  const fm_u32x4* wg =
+      reinterpret_cast<const fm_u32x4*>(packed) + gc * 4 * kc * 64 + lane;
+  const uint32_t* sg =
+      reinterpret_cast<const uint32_t*>(scales) + gc * kc * 64 + lane;
+
+  // staging of x: the BM x 256 B chunk is BM x 16 pieces of 16 B, PX per
+  // thread, 16 consecutive threads one row; THREADS % 16 == 0, so all of
+  // a thread's pieces have the same k
+  const int col = tid & 15;
+  const bool tail_valid = FM_KCHUNK * (kc - 1) + 8 * col < K;
+  const uint16_t* xg[PX];
+#pragma unroll
+  for (int i = 0; i < PX; ++i) {
+    const int row = (tid >> 4) + (THREADS / 16) * i;
+    const int gm = m0 + row < M ? m0 + row : M - 1;
+    xg[i] = x + (long)gm * K;
+  }
+  const int xs = (tid >> 4) * FMG_ROW_U4 + col;
+  fm_u32x4 xr[PX];
+  auto load_x = [&](int c) __attribute__((always_inline)) {
+    const bool valid = c + 1 < kc || tail_valid;
+    const long k = valid ? (long)FM_KCHUNK * c + 8 * col : 0;
+#pragma unroll
+    for (int i = 0; i < PX; ++i)
+      xr[i] = *reinterpret_cast<const fm_u32x4*>(xg[i] + k);
+  };
+  auto store_x = [&](int c) __attribute__((always_inline)) {
+    const uint32_t mask = c + 1 < kc || tail_valid ? 0xFFFFFFFFu : 0u;
+#pragma unroll
+    for (int i = 0; i < PX; ++i)
+      s_x[c & 1][xs + (THREADS / 16) * FMG_ROW_U4 * i] = xr[i] & mask;
+  };
+
+  fm_frag_cd acc[4][MT];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < MT; ++j) acc[i][j] = fm_frag_cd{0.f, 0.f, 0.f, 0.f};
+
+  const int sx0 = FMG_ROW_U4 * r + 4 * q;
+  fmg_stage s0, s1, s2;
+  load_x(0);
+  fmg_load_codes(s0, wg, sg, 0, kc);
+  store_x(0);
+  if (kc == 1) {
+    fm_barrier();
+    fmg_compute<MT>(&s_x[0][sx0], s0, acc);
+  } else {
+    load_x(1);
+    fmg_load_codes(s1, wg, sg, 1, kc);
+    fm_barrier();
+    // one step: x of chunk c + 1 to LDS, the loads of chunk c + 2 into
+    // the free stage, chunk c from the stage loaded two steps ago
+    auto step = [&](int c, const fmg_stage& cur, fmg_stage& free)
+                    __attribute__((always_inline)) {
+      store_x(c + 1);
+      load_x(c + 2);
+      fmg_load_codes(free, wg, sg, c + 2, kc);
+      __builtin_amdgcn_sched_barrier(0);
+      fmg_compute<MT>(&s_x[c & 1][sx0], cur, acc);
+      __builtin_amdgcn_sched_barrier(0);
+      fm_barrier();
+    };
+    // steady loop: three steps, so that the stages rotate by name. (By
+    // register moves the move of a stage would wait for the load just
+    // issued into it.)
+    int c = 0;
+    for (; c + 4 < kc; c += 3) {
+      step(c, s0, s2);
+      step(c + 1, s1, s0);
+      step(c + 2, s2, s1);
+    }
+    // tail: at most two more steps, whose moves do wait for their loads,
+    // then chunks kc - 2 and kc - 1 with nothing left to load
+    for (; c + 2 < kc; ++c) {
+      step(c, s0, s2);
+      fmg_move(s0, s1);
+      fmg_move(s1, s2);
+    }
+    store_x(c + 1);
+    fmg_compute<MT>(&s_x[c & 1][sx0], s0, acc);
+    fm_barrier();
+    fmg_compute<MT>(&s_x[(c + 1) & 1][sx0], s1, acc);
+  }
+
+  // D[n = 4 q + e][m = r] in acc[i][j][e]: a lane holds four consecutive n
+  // of one row of y
+  const bool vec = (N & 3) == 0 && ((uintptr_t)y & 7) == 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const long n = group * FM_GROUP + 16 * i + 4 * q;
+#pragma unroll
+    for (int j = 0; j < MT; ++j) {
+      const int m = m0 + 16 * j + r;
+      if (m >= M || n >= N) continue;
+      uint16_t o[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = fm_bf16_rne(acc[i][j][e]);
+      uint16_t* dst = y + (long)m * N + n;
+      if (vec) {
+        // (HIP's uint2 has a constructor, which this kernel's target
+        // attribute would turn into a real call)
+        *reinterpret_cast<fm_u32x2*>(dst) =
+            fm_u32x2{(uint32_t)o[0] | ((uint32_t)o[1] << 16),
+                     (uint32_t)o[2] | ((uint32_t)o[3] << 16)};
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (n + e < N) dst[e] = o[e];
+      }
+    }
+  }
+}
+
 // One 16-byte lane load (one MX block of one row) per item, four 16-byte
 // stores of bf16: a lane's 64 B are contiguous in its row.
 extern "C" __global__ void FM_KERNEL_ATTR __launch_bounds__(256)
@@ -344,6 +605,68 @@ extern "C" hipError_t ca_mxfp4w_decode_gemm_bf16(const void* x,
     if (fm_waves_for(K) == 16) FM_LAUNCH(2, 16); else FM_LAUNCH(2, 4);
   }
 #undef FM_LAUNCH
+  return hipGetLastError();
+}
+
+namespace {
+
+#define FMG_MIN_BLOCKS 192  // three quarters of the 256 CUs
+
+inline long fmg_blocks(int M, int N, int bn, int bm) {
+  return (((long)N + bn - 1) / bn) * (((long)M + bm - 1) / bm);
+}
+
+// The wide GEMM's variant as 1000 BN + BM, from (M, N) alone: the largest
+// tile that is more than half rows of x (not mostly padding) and whose
+// grid has at least FMG_MIN_BLOCKS workgroups; 64 x 32 where none has.
+// Larger tiles read the codes fewer times (M / BM) and share x among more
+// waves; smaller ones fill the CUs, and with one wave per 64-row group
+// and no K split that is what most decoder shapes lack: a 128-row chunk
+// reads every code once (256 x 128) only where N >= 192 x 256.
+inline int fmg_tile_for(int M, int N) {
+  if (M > 64 && fmg_blocks(M, N, 256, 128) >= FMG_MIN_BLOCKS) return 256128;
+  if (M > 32 && fmg_blocks(M, N, 128, 64) >= FMG_MIN_BLOCKS) return 128064;
+  return 64032;
+}
+
+}  // namespace
+
+// The variant ca_mxfp4w_gemm_bf16 uses for (M, N) as 1000 BN + BM (64032,
+// 128064 or 256128); 0 outside its contract.
+extern "C" int ca_mxfp4w_gemm_tile(int M, int N) {
+  return M < 1 || N < 1 ? 0 : fmg_tile_for(M, N);
+}
+
+// The decode GEMM's semantics without its limit on M: x [M, K] bf16, codes
+// and scales of W[N, K] in the layout above, y [M, N] bf16. M >= 1, N >= 1,
+// K >= 32, K % 32 == 0; x and codes 16-byte, scales 4-byte, y 2-byte
+// aligned. Anything else returns hipErrorInvalidValue before any launch.
+// No workspace, no atomics.
+extern "C" hipError_t ca_mxfp4w_gemm_bf16(const void* x, const void* codes,
+                                          const void* scales, void* y, int M,
+                                          int N, int K, hipStream_t stream) {
+  if (M < 1 || N < 1 || K < FM_BLOCK || K % FM_BLOCK != 0)
+    return hipErrorInvalidValue;
+  if (!x || !codes || !scales || !y) return hipErrorInvalidValue;
+  if (((uintptr_t)x | (uintptr_t)codes) % 16 != 0 ||
+      (uintptr_t)scales % 4 != 0 || (uintptr_t)y % 2 != 0)
+    return hipErrorInvalidValue;
+  const int tile = fmg_tile_for(M, N);
+  const int bn = tile / 1000, bm = tile % 1000;
+  const long blocks = fmg_blocks(M, N, bn, bm);
+  if (blocks > 0x7FFFFFFFL) return hipErrorInvalidValue;
+  const int mblocks = (int)(((long)M + bm - 1) / bm);
+#define FMG_LAUNCH(WAVES, MT)                                              \
+  hipLaunchKernelGGL((mxfp4w_gemm_kernel<WAVES, MT>),                      \
+                     dim3((uint32_t)blocks), dim3(WAVES * 64), 0, stream,  \
+                     (const uint16_t*)x, (const uint8_t*)codes,            \
+                     (const uint8_t*)scales, (uint16_t*)y, M, N, K, mblocks)
+  switch (tile) {
+    case 256128: FMG_LAUNCH(4, 8); break;
+    case 128064: FMG_LAUNCH(2, 4); break;
+    default: FMG_LAUNCH(1, 2); break;
+  }
+#undef FMG_LAUNCH
   return hipGetLastError();
 }
 

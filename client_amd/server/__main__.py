@@ -16,7 +16,7 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
                decode_max_batch=8, prewarm_sampling=False,
                kv_cache_dtype=None, fused_prefill=False,
                weight_dtype=None, bert_fused_attention=False,
-               fp8_weight_gemm=False):
+               fp8_weight_gemm=False, mxfp4_weight_gemm=False):
     from . import (
         AddSubModel,
         IdentityModel,
@@ -28,6 +28,8 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
 
     if fp8_weight_gemm and weight_dtype != "fp8_e4m3":
         raise SystemExit("--fp8-weight-gemm needs --weight-dtype fp8_e4m3")
+    if mxfp4_weight_gemm and weight_dtype != "mxfp4":
+        raise SystemExit("--mxfp4-weight-gemm needs --weight-dtype mxfp4")
     core = InferenceCore()
     for name in model_names:
         if name == "identity_fp32":
@@ -135,7 +137,8 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
                               kv_cache_dtype=kv_cache_dtype,
                               fused_prefill=fused_prefill,
                               weight_dtype=weight_dtype,
-                              fp8_weight_gemm=fp8_weight_gemm)
+                              fp8_weight_gemm=fp8_weight_gemm,
+                              mxfp4_weight_gemm=mxfp4_weight_gemm)
             )
         elif name == "ensemble_image":
             # preprocess (HIP kernel on GPU) -> resnet50 pipeline; the
@@ -224,6 +227,12 @@ def build_parser():
                              "decode steps of more than 16 slots) on the "
                              "fp8-weight MFMA GEMM kernel instead of "
                              "dequantising the layer for the library GEMM")
+    parser.add_argument("--mxfp4-weight-gemm", action="store_true",
+                        help="with --weight-dtype mxfp4: run linear calls "
+                             "of more than 16 rows (prefill chunks, decode "
+                             "steps of more than 16 slots) on the "
+                             "MXFP4-weight MFMA GEMM kernel instead of "
+                             "dequantising the layer for the library GEMM")
     parser.add_argument("--fused-prefill", action="store_true",
                         help="run the prefill chunks of generate models on "
                              "the fused RoPE + scatter and MFMA attention "
@@ -257,6 +266,7 @@ def main(argv=None):
         weight_dtype=args.weight_dtype,
         bert_fused_attention=args.bert_fused_attention,
         fp8_weight_gemm=args.fp8_weight_gemm,
+        mxfp4_weight_gemm=args.mxfp4_weight_gemm,
     )
     if args.dynamic_batching:
         for model in core.models.values():

@@ -281,12 +281,18 @@ class GenerateModel(Model):
     ValueError) runs the e4m3 layers' calls of more than 16 rows, prefill
     chunks and wide decode steps, on the fp8-weight MFMA GEMM instead of
     the dequant route; the served config then carries an
-    ``fp8_weight_gemm`` parameter."""
+    ``fp8_weight_gemm`` parameter.
+
+    ``mxfp4_weight_gemm`` (only with ``weight_dtype`` "mxfp4", otherwise
+    ValueError) does the same for the MXFP4 layers with the MXFP4-weight
+    MFMA GEMM; the served config then carries an ``mxfp4_weight_gemm``
+    parameter."""
 
     def __init__(self, name, llama_module, device="cuda:0", dtype=None,
                  use_scheduler=True, max_batch=8, prewarm_sampling=False,
                  kv_cache_dtype=None, fused_prefill=False,
-                 weight_dtype=None, fp8_weight_gemm=False):
+                 weight_dtype=None, fp8_weight_gemm=False,
+                 mxfp4_weight_gemm=False):
         super().__init__(
             name,
             [("input_ids", "INT64", [-1]), ("max_tokens", "INT32", [1]),
@@ -314,9 +320,14 @@ class GenerateModel(Model):
         if self.fp8_weight_gemm and self.weight_dtype != "fp8_e4m3":
             raise ValueError("fp8_weight_gemm needs weight_dtype "
                              f"'fp8_e4m3', not {weight_dtype!r}")
+        self.mxfp4_weight_gemm = bool(mxfp4_weight_gemm)
+        if self.mxfp4_weight_gemm and self.weight_dtype != "mxfp4":
+            raise ValueError("mxfp4_weight_gemm needs weight_dtype "
+                             f"'mxfp4', not {weight_dtype!r}")
         if self.weight_dtype is not None:
             quantize_llama_weights_as(self.module, self.weight_dtype,
-                                      fused_gemm=self.fp8_weight_gemm)
+                                      fused_gemm=self.fp8_weight_gemm,
+                                      wide_gemm=self.mxfp4_weight_gemm)
         self.fused_prefill = bool(fused_prefill)
         if self.fused_prefill:
             self.module.fused_prefill = True
@@ -345,6 +356,8 @@ class GenerateModel(Model):
             params["weight_dtype"] = {"string_value": self.weight_dtype}
         if self.fp8_weight_gemm:
             params["fp8_weight_gemm"] = {"string_value": "true"}
+        if self.mxfp4_weight_gemm:
+            params["mxfp4_weight_gemm"] = {"string_value": "true"}
         if self.fused_prefill:
             params["fused_prefill"] = {"string_value": "true"}
         if params:
