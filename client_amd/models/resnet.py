@@ -309,17 +309,132 @@ class Conv3x3BiasAct(nn.Module):
         return out
 
 
+# (C_in, C_out, H, W, mode) of the stride-1 1x1 convs that run on the
+# fused conv1x1 kernel; mode "act" is conv1 -> BiasAct, "res" is conv3 ->
+# BiasResAct. A shape/mode is listed only if the kernel's slowest round
+# was below the library path's fastest at batch 8 and at batch 32
+# (scripts/bench_conv1x1.py; docs/PERFORMANCE.md has every candidate's
+# numbers). Every other shape keeps the library conv and its epilogue
+# pass.
+CONV1X1_TABLE = frozenset({
+    (64, 64, 56, 56, "act"),
+    (256, 64, 56, 56, "act"),
+    (256, 128, 56, 56, "act"),
+    (512, 128, 28, 28, "act"),
+    (512, 256, 28, 28, "act"),
+    (64, 256, 56, 56, "res"),
+    (128, 512, 28, 28, "res"),
+    (256, 1024, 14, 14, "res"),
+})
+
+
+def pack_conv1x1_weight(weight):
+    """[K, C, 1, 1] -> [C/16, K, 16] contiguous: pack_conv3x3_weight's
+    layout with one tap, in which an MFMA A fragment (32 output channels
+    x 16 input channels) is a contiguous 1 KB."""
+    k, c = weight.shape[:2]
+    return (weight.detach().reshape(k, c // 16, 16).permute(1, 0, 2)
+            .contiguous())
+
+
+class Conv1x1BiasAct(nn.Module):
+    """conv1 -> BiasAct or conv3 -> BiasResAct of a bottleneck as ONE
+    CDNA4 kernel: a stride-1 1x1 conv on the matrix cores reading and
+    writing NCHW, with bias (+ residual) + ReLU applied from the
+    accumulators, so the conv output is never written and read back and
+    the residual is read once.
+
+    Like Conv3x3BiasAct the module owns no parameters: it is handed the
+    conv and the module that holds the fp32 bias (a BiasAct or a
+    BiasResAct, whose `forward` it does not call), and keeps the weights
+    repacked for the kernel keyed on the weight's storage and version,
+    built on the first GPU call (the eager warm-up, before hipGraph
+    capture). `eligible` says whether a call can take the kernel; the
+    caller falls back to the library conv and the epilogue pass
+    otherwise."""
+
+    def __init__(self):
+        super().__init__()
+        self._packed = None
+        self._key = None
+        self.calls = 0  # kernel launches (tests assert it really ran)
+
+    @staticmethod
+    def eligible(x, conv, residual=None):
+        import torch
+
+        if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
+                and x.is_contiguous()):
+            return False
+        if (os.environ.get("CLIENT_AMD_FUSED_BIAS", "1") == "0"
+                or os.environ.get("CLIENT_AMD_CONV1X1", "1") == "0"):
+            return False
+        w = conv.weight
+        if not (conv.bias is None and conv.kernel_size == (1, 1)
+                and conv.padding == (0, 0) and conv.dilation == (1, 1)
+                and conv.groups == 1 and conv.stride == (1, 1)
+                and w.dtype == torch.bfloat16 and w.device == x.device):
+            return False
+        if residual is not None and not (
+                residual.dtype == torch.bfloat16
+                and residual.device == x.device
+                and residual.shape == (x.shape[0], w.shape[0], x.shape[2],
+                                       x.shape[3])
+                and residual.is_contiguous()):
+            return False
+        return (w.shape[1], w.shape[0], x.shape[2], x.shape[3],
+                "act" if residual is None else "res") in CONV1X1_TABLE
+
+    def _weights(self, w):
+        try:
+            version = w._version
+        except RuntimeError:  # inference tensors track no version
+            version = 0
+        key = (w.data_ptr(), version)
+        if self._key != key:
+            self._packed = pack_conv1x1_weight(w)
+            self._key = key
+        return self._packed
+
+    def forward(self, x, conv, ba, residual=None, relu=True):
+        """ba: the module whose fp32 `bias` buffer is added; residual:
+        the block's identity for the exit mode, None for conv1."""
+        import torch
+
+        from ..ops import hip_runtime as hr
+
+        if ba.bias.dtype != torch.float32:
+            # TorchModel's .to(bf16) sweeps buffers; kernel reads fp32
+            ba.bias.data = ba.bias.data.float()
+        n, c, h, w = x.shape
+        k = conv.weight.shape[0]
+        out = torch.empty((n, k, h, w), device=x.device, dtype=x.dtype)
+        hr.conv1x1_bias_act_bf16(
+            x.data_ptr(), self._weights(conv.weight).data_ptr(),
+            ba.bias.data_ptr(),
+            0 if residual is None else residual.data_ptr(), out.data_ptr(),
+            n, c, k, h, w, relu, torch.cuda.current_stream().cuda_stream)
+        self.calls += 1
+        return out
+
+
 class FusedBottleneck(nn.Module):
     """Bottleneck with BN folded into the convs and every elementwise
     epilogue fused into one-pass CDNA4 kernels:
 
-        conv1 -> BiasAct(relu)     1 pass  (was bias add + relu = 2)
+        conv1 -> BiasAct(relu)     1 pass  (was bias add + relu = 2); one
+                                   Conv1x1BiasAct kernel for the shapes
+                                   in CONV1X1_TABLE
+                                   (CLIENT_AMD_CONV1X1=0 disables)
         conv2 -> BiasAct(relu)     1 pass; one Conv3x3BiasAct kernel for
                                    the shapes in CONV3X3_TABLE
                                    (CLIENT_AMD_CONV3X3=0 disables)
         conv3 (biasless), identity = downsample conv (biasless) or x
               -> BiasResAct        1 pass  (was bias [+ds bias] + add
-                                            + relu = 3-4 passes)
+                                            + relu = 3-4 passes); one
+                                   Conv1x1BiasAct kernel with the
+                                   identity as its residual for the
+                                   shapes in CONV1X1_TABLE
 
     The downsample conv's folded bias is per-channel on the same C as
     conv3's, so it is pre-summed into the exit bias."""
@@ -332,14 +447,22 @@ class FusedBottleneck(nn.Module):
         self.ds_conv = ds_conv
         self.exit = BiasResAct(exit_bias)
         self.conv3x3 = Conv3x3BiasAct()
+        self.conv1x1_in = Conv1x1BiasAct()
+        self.conv1x1_exit = Conv1x1BiasAct()
 
     def forward(self, x):
         identity = self.ds_conv(x) if self.ds_conv is not None else x
-        out = self.ba1(self.conv1(x))
+        if Conv1x1BiasAct.eligible(x, self.conv1):
+            out = self.conv1x1_in(x, self.conv1, self.ba1,
+                                  relu=self.ba1.relu_flag)
+        else:
+            out = self.ba1(self.conv1(x))
         if Conv3x3BiasAct.eligible(out, self.conv2):
             out = self.conv3x3(out, self.conv2, self.ba2)
         else:
             out = self.ba2(self.conv2(out))
+        if Conv1x1BiasAct.eligible(out, self.conv3, identity):
+            return self.conv1x1_exit(out, self.conv3, self.exit, identity)
         out = self.conv3(out)
         return self.exit(out, identity)
 

@@ -20,6 +20,8 @@
 //     bias_relu_maxpool_bf16 (ResNet50 conv epilogues, NCHW and NHWC)
 //   - conv3x3_bias_act_bf16 (ResNet50 bottleneck 3x3 conv + bias + ReLU
 //     on the matrix cores, NCHW)
+//   - conv1x1_bias_act_bf16 (bottleneck 1x1 conv + bias (+ residual) +
+//     ReLU on the matrix cores, NCHW)
 //   - rmsnorm_bf16 / rope_decode_bf16 / rope_scatter_decode_bf16 /
 //     decode_gemm_bf16 / sample_logits_bf16 (LLM decode step)
 //     fp8w_decode_gemm_bf16 / fp8w_gemm_bf16 + fp8w_gemm_tile /
@@ -354,6 +356,21 @@ static bool conv3x3_supported(int n, int c, int k, int h, int w, int stride) {
   return c3_plan(&g, n, c, k, h, w, stride);
 }
 
+static void conv1x1_bias_act_bf16(uintptr_t x, uintptr_t w_packed,
+                                  uintptr_t bias, uintptr_t residual,
+                                  uintptr_t out, int n, int c, int k, int h,
+                                  int w, bool relu, uintptr_t stream_handle) {
+  HIP_CHECK(ca_conv1x1_bias_act_bf16(
+      cptr(x), cptr(w_packed), cptr(bias), cptr(residual), mptr(out), n, c, k,
+      h, w, relu ? 1 : 0, reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
+// true when ca_conv1x1_bias_act_bf16 accepts the shape (host-side check)
+static bool conv1x1_supported(int n, int c, int k, int h, int w) {
+  Conv1x1Geom g;
+  return c1_plan(&g, n, c, k, h, w);
+}
+
 static void decode_gemm_bf16(uintptr_t x, uintptr_t w, uintptr_t y, int n,
                              int k, uintptr_t stream_handle) {
   HIP_CHECK(ca_decode_gemm_bf16(
@@ -631,6 +648,13 @@ PYBIND11_MODULE(_hip_c, m) {
         py::arg("stride"), py::arg("relu"), py::arg("stream_handle"));
   m.def("conv3x3_supported", &conv3x3_supported, py::arg("n"), py::arg("c"),
         py::arg("k"), py::arg("h"), py::arg("w"), py::arg("stride"));
+  m.def("conv1x1_bias_act_bf16", &conv1x1_bias_act_bf16, py::arg("x"),
+        py::arg("w_packed"), py::arg("bias"), py::arg("residual"),
+        py::arg("out"), py::arg("n"), py::arg("c"), py::arg("k"),
+        py::arg("h"), py::arg("w"), py::arg("relu"),
+        py::arg("stream_handle"));
+  m.def("conv1x1_supported", &conv1x1_supported, py::arg("n"), py::arg("c"),
+        py::arg("k"), py::arg("h"), py::arg("w"));
   m.def("bias_res_act_bf16", &bias_res_act_bf16, py::arg("x"), py::arg("res"),
         py::arg("bias"), py::arg("out"), py::arg("n_planes"), py::arg("plane"),
         py::arg("channels"), py::arg("relu"), py::arg("stream_handle"));

@@ -2120,6 +2120,10 @@ extern "C" hipError_t ca_bias_act_bf16(const void* x, const void* bias,
 // fused 3x3 conv + bias + ReLU (shares epilogue_finish with the above)
 #include "conv3x3.hip"
 
+// fused 1x1 conv + bias (+ residual) + ReLU (shares epilogue_pair and
+// epilogue_finish with the above)
+#include "conv1x1.hip"
+
 // Channels-LAST (NHWC-contiguous) variant: channel is the fastest
 // dim, so each lane's 8 consecutive elements are 8 consecutive
 // channels — loads of x, residual AND bias all coalesce. This is what
