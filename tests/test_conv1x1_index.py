@@ -37,6 +37,20 @@ TESTED = [
     (1, 64, 256, 56, 56), (6, 64, 256, 56, 56), (2, 64, 64, 4, 6),
     (336, 64, 256, 7, 7), (42, 64, 512, 14, 14),
 ]
+# ... and of tests/test_conv_rounding_gpu.py with the variant each was
+# chosen to reach: the smallest batches at which K = 2048 gives the 512
+# workgroups of the 128-column kernels
+ROUNDING = {
+    (3, 96, 64, 7, 7): "NT=1 VL=1 VS=0",
+    (2, 64, 128, 14, 14): "NT=1 VL=2 VS=0",
+    (2, 96, 64, 4, 6): "NT=1 VL=2 VS=1",
+    (1, 32, 64, 1, 1): "NT=1 VL=1 VS=0",
+    (2, 2048, 64, 7, 7): "NT=1 VL=1 VS=0",
+    (40, 32, 2048, 7, 7): "NT=2 VL=1 VS=0",
+    (10, 32, 2048, 14, 14): "NT=2 VL=2 VS=0",
+    (31, 32, 2048, 8, 8): "NT=2 VL=2 VS=1",
+}
+TESTED += [c for c in ROUNDING if c not in TESTED]
 
 PROGRAM = r"""
 #include <cstdio>
@@ -236,6 +250,20 @@ def test_every_kernel_variant_is_walked(checker):
         seen.add(tuple(_run(checker, *case).split()[1:4]))
     assert seen == {(f"NT={nt}", f"VL={vl}", f"VS={vs}")
                     for nt in (1, 2) for vl, vs in ((1, 0), (2, 0), (2, 1))}
+
+
+def test_rounding_test_shapes_reach_their_variants(checker):
+    import conv_refs as cr
+
+    assert set(cr.CONV1X1_SHAPES) == set(ROUNDING)
+    assert set(cr.CONV1X1_INTERVAL_SHAPES
+               + cr.CONV1X1_NONFINITE_SHAPES) <= set(ROUNDING)
+    for case, variant in ROUNDING.items():
+        assert _run(checker, *case).split()[1:4] == variant.split(), case
+    # one image fewer and the 128-column cases fall to the 64-column kernel
+    for case in ((39, 32, 2048, 7, 7), (9, 32, 2048, 14, 14),
+                 (30, 32, 2048, 8, 8)):
+        assert _run(checker, *case).split()[1] == "NT=1", case
 
 
 @pytest.mark.parametrize("case", [

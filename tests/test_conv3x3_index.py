@@ -41,6 +41,13 @@ TESTED = [
     (32, 64, 1, 1, 1),
     (64, 64, 64, 3, 2),
     (64, 64, 3, 64, 1),
+    # ... and those of tests/test_conv_rounding_gpu.py
+    (32, 64, 7, 7, 1),
+    (32, 128, 9, 5, 1),
+    (64, 64, 7, 7, 2),
+    (32, 64, 8, 8, 2),
+    (512, 64, 7, 7, 1),
+    (32, 512, 8, 8, 1),
 ]
 
 PROGRAM = r"""
@@ -178,6 +185,22 @@ def test_every_offset_in_bounds_and_written_once(checker, shape):
     for n in (1, 2, 3, 32):
         out = _run(checker, n, shape)
         assert out.startswith("OK"), (n, out)
+
+
+def test_rounding_test_shapes_at_their_batch_sizes(checker):
+    """The cases of tests/test_conv_rounding_gpu.py at the batch sizes
+    they run with: N = 127 is the smallest batch of 8x8 planes with
+    K = 512 that takes the 128-column kernel (64 tiles x 8 channel rows
+    = 512 workgroups), everything else takes the 64-column one."""
+    import conv_refs as cr
+
+    assert {s[1:] for s in cr.CONV3X3_SHAPES} <= set(TESTED)
+    for case in cr.CONV3X3_SHAPES:
+        out = _run(checker, case[0], case[1:])
+        want = "NT=2" if case == (127, 32, 512, 8, 8, 1) else "NT=1"
+        assert out.startswith("OK") and out.split()[1] == want, (case, out)
+    assert (127, 32, 512, 8, 8, 1) in cr.CONV3X3_SHAPES
+    assert _run(checker, 126, (32, 512, 8, 8, 1)).split()[1] == "NT=1"
 
 
 @pytest.mark.parametrize("shape", [
