@@ -20,6 +20,8 @@ KERNEL_INCLUDES = (OPS_DIR / "csrc" / "conv3x3.hip",
                    OPS_DIR / "csrc" / "conv3x3_index.h",
                    OPS_DIR / "csrc" / "conv1x1.hip",
                    OPS_DIR / "csrc" / "conv1x1_index.h",
+                   OPS_DIR / "csrc" / "dense_layer.hip",
+                   OPS_DIR / "csrc" / "dense_layer_index.h",
                    OPS_DIR / "csrc" / "prefill_attention.hip",
                    OPS_DIR / "csrc" / "encoder_attention.hip",
                    OPS_DIR / "csrc" / "weight_fp8.hip",

@@ -22,6 +22,9 @@
 //     on the matrix cores, NCHW)
 //   - conv1x1_bias_act_bf16 (bottleneck 1x1 conv + bias (+ residual) +
 //     ReLU on the matrix cores, NCHW)
+//   - dense_conv1x1_bf16 / dense_conv3x3_k32_bf16 (DenseNet dense layer
+//     on a block buffer: BN+ReLU prologue + 1x1 conv + bias + ReLU, and
+//     the 3x3 growth conv stored at a channel offset of the buffer)
 //   - rmsnorm_bf16 / rope_decode_bf16 / rope_scatter_decode_bf16 /
 //     decode_gemm_bf16 / sample_logits_bf16 (LLM decode step)
 //     fp8w_decode_gemm_bf16 / fp8w_gemm_bf16 + fp8w_gemm_tile /
@@ -371,6 +374,53 @@ static bool conv1x1_supported(int n, int c, int k, int h, int w) {
   return c1_plan(&g, n, c, k, h, w);
 }
 
+static void dense_conv1x1_bf16(uintptr_t x, long xs, uintptr_t scale,
+                               uintptr_t shift, uintptr_t w_packed,
+                               uintptr_t bias, uintptr_t out, int n, int c,
+                               int k, int h, int w, bool relu,
+                               uintptr_t stream_handle) {
+  HIP_CHECK(ca_dense_conv1x1_bf16(
+      cptr(x), xs, cptr(scale), cptr(shift), cptr(w_packed), cptr(bias),
+      mptr(out), n, c, k, h, w, relu ? 1 : 0,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
+// true when ca_dense_conv1x1_bf16 accepts the shape (host-side check)
+static bool dense_conv1x1_supported(int n, int c, int k, int h, int w,
+                                    long xs) {
+  DenseConv1x1Geom g;
+  return dl_plan_a(&g, n, c, k, h, w, xs);
+}
+
+// columns per workgroup the plan picks (64 or 128), 0 when unsupported
+static int dense_conv1x1_tile(int n, int c, int k, int h, int w, long xs) {
+  DenseConv1x1Geom g;
+  return dl_plan_a(&g, n, c, k, h, w, xs) ? c1_bn(g.c) : 0;
+}
+
+static void dense_conv3x3_k32_bf16(uintptr_t x, uintptr_t w_packed,
+                                   uintptr_t out, int n, int c, int h, int w,
+                                   int k0, long os,
+                                   uintptr_t stream_handle) {
+  HIP_CHECK(ca_dense_conv3x3_k32_bf16(
+      cptr(x), cptr(w_packed), mptr(out), n, c, h, w, k0, os,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
+// true when ca_dense_conv3x3_k32_bf16 accepts the shape and the slot
+static bool dense_conv3x3_k32_supported(int n, int c, int h, int w, int k0,
+                                        long os) {
+  DenseConv3x3Geom g;
+  return dl_plan_b(&g, n, c, h, w, k0, os);
+}
+
+// output rows per workgroup the plan picks, 0 when unsupported
+static int dense_conv3x3_k32_rows(int n, int c, int h, int w, int k0,
+                                  long os) {
+  DenseConv3x3Geom g;
+  return dl_plan_b(&g, n, c, h, w, k0, os) ? g.R : 0;
+}
+
 static void decode_gemm_bf16(uintptr_t x, uintptr_t w, uintptr_t y, int n,
                              int k, uintptr_t stream_handle) {
   HIP_CHECK(ca_decode_gemm_bf16(
@@ -655,6 +705,27 @@ PYBIND11_MODULE(_hip_c, m) {
         py::arg("stream_handle"));
   m.def("conv1x1_supported", &conv1x1_supported, py::arg("n"), py::arg("c"),
         py::arg("k"), py::arg("h"), py::arg("w"));
+  m.def("dense_conv1x1_bf16", &dense_conv1x1_bf16, py::arg("x"),
+        py::arg("xs"), py::arg("scale"), py::arg("shift"),
+        py::arg("w_packed"), py::arg("bias"), py::arg("out"), py::arg("n"),
+        py::arg("c"), py::arg("k"), py::arg("h"), py::arg("w"),
+        py::arg("relu"), py::arg("stream_handle"));
+  m.def("dense_conv1x1_supported", &dense_conv1x1_supported, py::arg("n"),
+        py::arg("c"), py::arg("k"), py::arg("h"), py::arg("w"),
+        py::arg("xs"));
+  m.def("dense_conv1x1_tile", &dense_conv1x1_tile, py::arg("n"),
+        py::arg("c"), py::arg("k"), py::arg("h"), py::arg("w"),
+        py::arg("xs"));
+  m.def("dense_conv3x3_k32_bf16", &dense_conv3x3_k32_bf16, py::arg("x"),
+        py::arg("w_packed"), py::arg("out"), py::arg("n"), py::arg("c"),
+        py::arg("h"), py::arg("w"), py::arg("k0"), py::arg("os"),
+        py::arg("stream_handle"));
+  m.def("dense_conv3x3_k32_supported", &dense_conv3x3_k32_supported,
+        py::arg("n"), py::arg("c"), py::arg("h"), py::arg("w"),
+        py::arg("k0"), py::arg("os"));
+  m.def("dense_conv3x3_k32_rows", &dense_conv3x3_k32_rows, py::arg("n"),
+        py::arg("c"), py::arg("h"), py::arg("w"), py::arg("k0"),
+        py::arg("os"));
   m.def("bias_res_act_bf16", &bias_res_act_bf16, py::arg("x"), py::arg("res"),
         py::arg("bias"), py::arg("out"), py::arg("n_planes"), py::arg("plane"),
         py::arg("channels"), py::arg("relu"), py::arg("stream_handle"));

@@ -2124,6 +2124,11 @@ extern "C" hipError_t ca_bias_act_bf16(const void* x, const void* bias,
 // epilogue_finish with the above)
 #include "conv1x1.hip"
 
+// DenseNet dense layer: BN+ReLU -> 1x1 conv -> bias+ReLU, and the 3x3
+// growth conv written into the block buffer (shares conv1x1.hip's
+// barrier and fragment types and the epilogue helpers above)
+#include "dense_layer.hip"
+
 // Channels-LAST (NHWC-contiguous) variant: channel is the fastest
 // dim, so each lane's 8 consecutive elements are 8 consecutive
 // channels — loads of x, residual AND bias all coalesce. This is what

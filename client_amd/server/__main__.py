@@ -16,7 +16,8 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
                decode_max_batch=8, prewarm_sampling=False,
                kv_cache_dtype=None, fused_prefill=False,
                weight_dtype=None, bert_fused_attention=False,
-               fp8_weight_gemm=False, mxfp4_weight_gemm=False):
+               fp8_weight_gemm=False, mxfp4_weight_gemm=False,
+               densenet_fused=False):
     from . import (
         AddSubModel,
         IdentityModel,
@@ -67,15 +68,19 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
         elif name == "densenet121":
             import torch
 
+            import os
+
             from ..models import densenet121
 
             tdt = {"bf16": torch.bfloat16, "fp16": torch.float16,
                    "fp32": torch.float32}[dtype]
             io_dt = {"bf16": "BF16", "fp16": "FP16", "fp32": "FP32"}[dtype]
+            fused = (densenet_fused or os.environ.get(
+                "CLIENT_AMD_DENSENET_FUSED") == "1")
             core.add_model(
                 TorchModel(
                     "densenet121",
-                    densenet121(),
+                    densenet121(fused=fused),
                     inputs=[("INPUT0", io_dt, [-1, 3, 224, 224])],
                     outputs=[("OUTPUT0", io_dt, [-1, 1000])],
                     device=device,
@@ -241,6 +246,12 @@ def build_parser():
                         help="run the attention of the BERT models on the "
                              "fused MFMA encoder-attention kernel instead "
                              "of torch's multi-head attention")
+    parser.add_argument("--densenet-fused", action="store_true",
+                        help="run the dense layers and transitions of "
+                             "densenet121 on the fused MFMA dense-layer "
+                             "kernels, each block on one buffer with no "
+                             "concat (CLIENT_AMD_DENSENET_FUSED=1 does the "
+                             "same)")
     parser.add_argument("--model-warmup", action="store_true",
                         help="pre-capture hipGraphs / prime MIOpen for the "
                              "serving batch sizes before READY is printed")
@@ -267,6 +278,7 @@ def main(argv=None):
         bert_fused_attention=args.bert_fused_attention,
         fp8_weight_gemm=args.fp8_weight_gemm,
         mxfp4_weight_gemm=args.mxfp4_weight_gemm,
+        densenet_fused=args.densenet_fused,
     )
     if args.dynamic_batching:
         for model in core.models.values():

@@ -610,9 +610,10 @@ class TorchModel(Model):
         for entry in cfg["input"]:
             if entry["name"] in self.optional_inputs:
                 entry["optional"] = True
-        if getattr(self.module, "fused_attention", False):
-            cfg["parameters"] = {
-                "fused_attention": {"string_value": "true"}}
+        for flag in ("fused_attention", "fused_dense_layers"):
+            if getattr(self.module, flag, False):
+                cfg.setdefault("parameters", {})[flag] = {
+                    "string_value": "true"}
         return cfg
 
     def enable_dynamic_batching(self, preferred_batch_size=32,
