@@ -8,7 +8,9 @@ Two forms. The default is the textbook module: seven launches per dense
 layer (BN, ReLU, 1x1 conv, BN, ReLU, 3x3 conv, cat). `fuse_dense_layers`
 (densenet121(fused=True), the server's --densenet-fused) puts every dense
 block on one buffer and every layer on the two kernels of
-client_amd/ops/csrc/dense_layer.hip.
+client_amd/ops/csrc/dense_layer.hip, and folds the stem's BN into its
+conv (FusedStem; one launch of client_amd/ops/csrc/stem_conv.hip with
+CLIENT_AMD_STEM_CONV=1, the server's --fused-stem).
 """
 
 import os
@@ -17,7 +19,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .resnet import pack_conv1x1_weight, pack_conv3x3_weight
+from .resnet import (_is_stem_pool, pack_conv1x1_weight, pack_conv3x3_weight,
+                     pack_stem_weight, stem_switch)
 
 
 class DenseLayer(nn.Module):
@@ -253,13 +256,79 @@ class FusedTransition(nn.Module):
         return self.pool(F.conv2d(a, wt))
 
 
+class FusedStem(nn.Module):
+    """The stem (7x7 stride-2 conv, BN, ReLU, 3x3 stride-2 max-pool) with
+    the BN folded into the conv: weight * scale per output channel, the
+    shift as a bias. With CLIENT_AMD_STEM_CONV=1, on a HIP device, for
+    contiguous bf16 input of a shape the kernel accepts it is one launch
+    of stem_conv7x7_pool_bf16 (client_amd/ops/csrc/stem_conv.hip);
+    otherwise the same folded algebra runs as torch ops."""
+
+    def __init__(self, conv, bn):
+        super().__init__()
+        scale, shift = _bn_affine(bn)
+        self.folded = _FoldedParams(
+            [(conv.weight.detach() * scale.view(-1, 1, 1, 1), shift)])
+        self.calls = 0  # kernel launches (tests assert it really ran)
+        self.enabled = None  # None: CLIENT_AMD_STEM_CONV decides
+
+    def forward(self, x):
+        use = (stem_switch(self.enabled) and x.is_cuda
+               and x.dtype == torch.bfloat16
+               and x.dim() == 4 and x.shape[1] == 3 and x.is_contiguous())
+        if use:
+            from ..ops import hip_runtime as hr
+
+            n, _, h, w = x.shape
+            use = hr.stem_conv7x7_pool_supported(n, h, w)
+        if use:
+            def build(wt, b):
+                dev = x.device
+                return (pack_stem_weight(wt.to(dev).to(torch.bfloat16)),
+                        b.float().to(dev))
+
+            (wp, b), = self.folded.get(x.device, x.dtype, "kernel", build)
+            oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+            out = torch.empty((n, 64, (oh - 1) // 2 + 1, (ow - 1) // 2 + 1),
+                              device=x.device, dtype=x.dtype)
+            hr.stem_conv7x7_pool_bf16(x.data_ptr(), wp.data_ptr(),
+                                      b.data_ptr(), out.data_ptr(), n, h, w,
+                                      _stream())
+            self.calls += 1
+            return out
+
+        def build(*tensors):
+            return tuple(t.to(x.device, x.dtype) for t in tensors)
+
+        (wt, b), = self.folded.get(x.device, x.dtype, "torch", build)
+        y = F.conv2d(x, wt, stride=2, padding=3) + b.view(1, -1, 1, 1)
+        return F.max_pool2d(y.relu_(), 3, 2, 1)
+
+
+def _is_textbook_stem(stem):
+    if not (isinstance(stem, nn.Sequential) and len(stem) == 4):
+        return False
+    conv, bn, relu, pool = stem
+    return (isinstance(conv, nn.Conv2d) and conv.bias is None
+            and tuple(conv.weight.shape) == (64, 3, 7, 7)
+            and conv.stride == (2, 2) and conv.padding == (3, 3)
+            and isinstance(bn, nn.BatchNorm2d)
+            and isinstance(relu, nn.ReLU) and _is_stem_pool(pool))
+
+
 def fuse_dense_layers(model):
     """Rewrite `model.features` (eval mode) so that each run of
     DenseLayers is one FusedDenseBlock and each Transition a
-    FusedTransition; sets `model.fused_dense_layers`. Convert before
-    moving the model to its serving dtype: the BN statistics are folded
-    in the dtype the model has now."""
+    FusedTransition, and `model.stem` as a FusedStem; sets
+    `model.fused_dense_layers`, and `model.fused_stem` when
+    CLIENT_AMD_STEM_CONV=1 now. Convert before moving the model to its
+    serving dtype: the BN statistics are folded in the dtype the model
+    has now."""
     model.eval()
+    if _is_textbook_stem(getattr(model, "stem", None)):
+        model.stem = FusedStem(model.stem[0], model.stem[1])
+        if stem_switch():
+            model.fused_stem = True
     out, run = [], []
     for m in model.features:
         if isinstance(m, DenseLayer):

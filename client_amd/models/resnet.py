@@ -67,7 +67,12 @@ class ResNet50(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        stem = getattr(self, "stem_fused", None)
+        if stem is not None and StemConvPool.eligible(
+                x, self.conv1, self.bn1, stem.enabled):
+            x = stem(x, self.conv1, self.bn1)
+        else:
+            x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
         x = self.layer1(x)
         x = self.layer2(x)
         x = self.layer3(x)
@@ -418,6 +423,110 @@ class Conv1x1BiasAct(nn.Module):
         return out
 
 
+def stem_switch(enabled=None):
+    """The fused stem kernel is opt-in: CLIENT_AMD_STEM_CONV=1, or a stem
+    module's `enabled = True` (what the server's --fused-stem sets, so
+    that the flag stays with the models of that server)."""
+    if enabled is not None:
+        return bool(enabled)
+    return os.environ.get("CLIENT_AMD_STEM_CONV", "0") == "1"
+
+
+def pack_stem_weight(weight):
+    """[64, 3, 7, 7] -> [2, 11, 2, 32, 8] contiguous: the stem kernel's
+    MFMA A fragments. K is ordered (ky, c, kx) with kx padded from 7 to 8
+    by a zero, which gives 21 groups of 8; a 22nd, all-zero group makes
+    11 steps of 16. Index [half, step, lh, lr, kx] holds output channel
+    32*half + lr, group 2*step + lh, so a wave's fragment of one step is
+    1 KB contiguous in lane order."""
+    k = weight.shape[0]
+    w = weight.detach().permute(0, 2, 1, 3).reshape(k, 21, 7)
+    padded = w.new_zeros((k, 22, 8))
+    padded[:, :21, :7] = w
+    return (padded.reshape(2, 32, 11, 2, 8).permute(0, 2, 3, 1, 4)
+            .contiguous())
+
+
+class StemConvPool(nn.Module):
+    """conv1 -> BiasReluMaxPool of the stem as ONE CDNA4 kernel: the 7x7
+    stride-2 conv on the matrix cores reading NCHW, each conv pixel
+    finished from the fp32 accumulator (fp32 bias add, ReLU, one RNE to
+    bf16: one rounding fewer than conv1 -> BiasReluMaxPool, which rounds
+    the conv output to bf16 in between; equal bits where the sums are
+    exact), the 3x3 stride-2 max-pool taken in LDS with
+    BiasReluMaxPool's NaN rule, and only the pooled map written.
+    The library path transposes the 3-channel input and the 64x112x112
+    map between NCHW and NHWC and accumulates with atomics.
+
+    Like Conv3x3BiasAct the module owns no parameters: it is handed the
+    stem conv and the module that holds the fp32 bias (a BiasReluMaxPool,
+    whose `forward` it does not call), and keeps the weights repacked
+    for the kernel keyed on the weight's storage and version, built on
+    the first GPU call (the eager warm-up, before hipGraph capture).
+    Opt-in: `eligible` is False unless CLIENT_AMD_STEM_CONV=1 or the
+    module's `enabled` is True."""
+
+    def __init__(self):
+        super().__init__()
+        self._packed = None
+        self._key = None
+        self.calls = 0  # kernel launches (tests assert it really ran)
+        self.enabled = None  # None: CLIENT_AMD_STEM_CONV decides
+
+    @staticmethod
+    def eligible(x, conv, pool, enabled=None):
+        import torch
+
+        if not (stem_switch(enabled) and x.is_cuda
+                and x.dtype == torch.bfloat16
+                and x.dim() == 4 and x.is_contiguous()):
+            return False
+        if os.environ.get("CLIENT_AMD_FUSED_BIAS", "1") == "0":
+            return False
+        w = conv.weight
+        if not (isinstance(pool, BiasReluMaxPool)
+                and conv.bias is None and tuple(w.shape) == (64, 3, 7, 7)
+                and x.shape[1] == 3 and conv.stride == (2, 2)
+                and conv.padding == (3, 3) and conv.dilation == (1, 1)
+                and conv.groups == 1 and conv.padding_mode == "zeros"
+                and w.dtype == torch.bfloat16 and w.device == x.device):
+            return False
+        from ..ops import hip_runtime as hr
+
+        return hr.stem_conv7x7_pool_supported(x.shape[0], x.shape[2],
+                                              x.shape[3])
+
+    def _weights(self, w):
+        try:
+            version = w._version
+        except RuntimeError:  # inference tensors track no version
+            version = 0
+        key = (w.data_ptr(), version)
+        if self._key != key:
+            self._packed = pack_stem_weight(w)
+            self._key = key
+        return self._packed
+
+    def forward(self, x, conv, pool):
+        import torch
+
+        from ..ops import hip_runtime as hr
+
+        if pool.bias.dtype != torch.float32:
+            # TorchModel's .to(bf16) sweeps buffers; kernel reads fp32
+            pool.bias.data = pool.bias.data.float()
+        n, _, h, w = x.shape
+        oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        out = torch.empty((n, 64, (oh - 1) // 2 + 1, (ow - 1) // 2 + 1),
+                          device=x.device, dtype=x.dtype)
+        hr.stem_conv7x7_pool_bf16(
+            x.data_ptr(), self._weights(conv.weight).data_ptr(),
+            pool.bias.data_ptr(), out.data_ptr(), n, h, w,
+            torch.cuda.current_stream().cuda_stream)
+        self.calls += 1
+        return out
+
+
 class FusedBottleneck(nn.Module):
     """Bottleneck with BN folded into the convs and every elementwise
     epilogue fused into one-pass CDNA4 kernels:
@@ -498,7 +607,9 @@ def fold_batchnorm(module, fuse_eltwise=None):
     BiasReluMaxPool pass (standing in the bn1 slot; relu and maxpool
     become Identity), so the folded conv biases never run as separate
     torch elementwise kernels
-    (default; CLIENT_AMD_FUSED_BIAS=0 disables). Pairs are detected by
+    (default; CLIENT_AMD_FUSED_BIAS=0 disables). The stem also gets a
+    `stem_fused` StemConvPool, which ResNet50.forward takes instead of
+    conv1 -> bn1 only when CLIENT_AMD_STEM_CONV=1. Pairs are detected by
     _modules adjacency (conv immediately followed by its BN, matching
     this file and torchvision layouts)."""
     from torch.nn.utils.fusion import fuse_conv_bn_eval
@@ -541,6 +652,9 @@ def fold_batchnorm(module, fuse_eltwise=None):
                     and _is_stem_pool(getattr(module, "maxpool", None))):
                 module.bn1 = BiasReluMaxPool(_strip_bias(fused))
                 module.maxpool = nn.Identity()
+                # the whole stem as one kernel when CLIENT_AMD_STEM_CONV=1
+                # (ResNet50.forward asks StemConvPool.eligible per call)
+                module.stem_fused = StemConvPool()
             else:
                 module.bn1 = BiasAct(_strip_bias(fused), relu=True)
             module.relu = nn.Identity()

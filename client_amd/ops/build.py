@@ -18,6 +18,8 @@ KERNELS = OPS_DIR / "csrc" / "kernels.hip"
 # files kernels.hip #includes
 KERNEL_INCLUDES = (OPS_DIR / "csrc" / "conv3x3.hip",
                    OPS_DIR / "csrc" / "conv3x3_index.h",
+                   OPS_DIR / "csrc" / "stem_conv.hip",
+                   OPS_DIR / "csrc" / "stem_conv_index.h",
                    OPS_DIR / "csrc" / "conv1x1.hip",
                    OPS_DIR / "csrc" / "conv1x1_index.h",
                    OPS_DIR / "csrc" / "dense_layer.hip",

@@ -20,6 +20,8 @@
 //     bias_relu_maxpool_bf16 (ResNet50 conv epilogues, NCHW and NHWC)
 //   - conv3x3_bias_act_bf16 (ResNet50 bottleneck 3x3 conv + bias + ReLU
 //     on the matrix cores, NCHW)
+//   - stem_conv7x7_pool_bf16 (ResNet50 / DenseNet stem: 7x7 conv + bias
+//     + ReLU + 3x3 max-pool on the matrix cores, conv map kept in LDS)
 //   - conv1x1_bias_act_bf16 (bottleneck 1x1 conv + bias (+ residual) +
 //     ReLU on the matrix cores, NCHW)
 //   - dense_conv1x1_bf16 / dense_conv3x3_k32_bf16 (DenseNet dense layer
@@ -357,6 +359,20 @@ static void conv3x3_bias_act_bf16(uintptr_t x, uintptr_t w_packed,
 static bool conv3x3_supported(int n, int c, int k, int h, int w, int stride) {
   Conv3x3Geom g;
   return c3_plan(&g, n, c, k, h, w, stride);
+}
+
+static void stem_conv7x7_pool_bf16(uintptr_t x, uintptr_t w_packed,
+                                   uintptr_t bias, uintptr_t out, int n,
+                                   int h, int w, uintptr_t stream_handle) {
+  HIP_CHECK(ca_stem_conv7x7_pool_bf16(
+      cptr(x), cptr(w_packed), cptr(bias), mptr(out), n, h, w,
+      reinterpret_cast<hipStream_t>(stream_handle)));
+}
+
+// true when ca_stem_conv7x7_pool_bf16 accepts the shape (host-side check)
+static bool stem_conv7x7_pool_supported(int n, int h, int w) {
+  StemGeom g;
+  return sc_plan(&g, n, h, w);
 }
 
 static void conv1x1_bias_act_bf16(uintptr_t x, uintptr_t w_packed,
@@ -698,6 +714,11 @@ PYBIND11_MODULE(_hip_c, m) {
         py::arg("stride"), py::arg("relu"), py::arg("stream_handle"));
   m.def("conv3x3_supported", &conv3x3_supported, py::arg("n"), py::arg("c"),
         py::arg("k"), py::arg("h"), py::arg("w"), py::arg("stride"));
+  m.def("stem_conv7x7_pool_bf16", &stem_conv7x7_pool_bf16, py::arg("x"),
+        py::arg("w_packed"), py::arg("bias"), py::arg("out"), py::arg("n"),
+        py::arg("h"), py::arg("w"), py::arg("stream_handle"));
+  m.def("stem_conv7x7_pool_supported", &stem_conv7x7_pool_supported,
+        py::arg("n"), py::arg("h"), py::arg("w"));
   m.def("conv1x1_bias_act_bf16", &conv1x1_bias_act_bf16, py::arg("x"),
         py::arg("w_packed"), py::arg("bias"), py::arg("residual"),
         py::arg("out"), py::arg("n"), py::arg("c"), py::arg("k"),

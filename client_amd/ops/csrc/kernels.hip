@@ -2120,6 +2120,10 @@ extern "C" hipError_t ca_bias_act_bf16(const void* x, const void* bias,
 // fused 3x3 conv + bias + ReLU (shares epilogue_finish with the above)
 #include "conv3x3.hip"
 
+// fused stem: 7x7 conv + bias + ReLU + 3x3 max-pool (shares the fragment
+// types with conv3x3.hip and epilogue_finish with the above)
+#include "stem_conv.hip"
+
 // fused 1x1 conv + bias (+ residual) + ReLU (shares epilogue_pair and
 // epilogue_finish with the above)
 #include "conv1x1.hip"

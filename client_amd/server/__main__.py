@@ -17,7 +17,9 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
                kv_cache_dtype=None, fused_prefill=False,
                weight_dtype=None, bert_fused_attention=False,
                fp8_weight_gemm=False, mxfp4_weight_gemm=False,
-               densenet_fused=False):
+               densenet_fused=False, fused_stem=False):
+    import os
+
     from . import (
         AddSubModel,
         IdentityModel,
@@ -31,6 +33,10 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
         raise SystemExit("--fp8-weight-gemm needs --weight-dtype fp8_e4m3")
     if mxfp4_weight_gemm and weight_dtype != "mxfp4":
         raise SystemExit("--mxfp4-weight-gemm needs --weight-dtype mxfp4")
+    # the flag is set on this core's stem modules, not in the environment;
+    # the kernel is bf16 only, so only a bf16 model advertises it
+    stem_on = ((fused_stem or os.environ.get("CLIENT_AMD_STEM_CONV") == "1")
+               and dtype == "bf16")
     core = InferenceCore()
     for name in model_names:
         if name == "identity_fp32":
@@ -55,10 +61,15 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
             tdt = {"bf16": torch.bfloat16, "fp16": torch.float16,
                    "fp32": torch.float32}[dtype]
             io_dt = {"bf16": "BF16", "fp16": "FP16", "fp32": "FP32"}[dtype]
+            module = resnet50()
+            stem = getattr(module, "stem_fused", None)
+            if stem is not None and stem_on:
+                stem.enabled = True
+                module.fused_stem = True
             core.add_model(
                 TorchModel(
                     "resnet50",
-                    resnet50(),
+                    module,
                     inputs=[("INPUT0", io_dt, [-1, 3, 224, 224])],
                     outputs=[("OUTPUT0", io_dt, [-1, 1000])],
                     device=device,
@@ -68,8 +79,6 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
         elif name == "densenet121":
             import torch
 
-            import os
-
             from ..models import densenet121
 
             tdt = {"bf16": torch.bfloat16, "fp16": torch.float16,
@@ -77,10 +86,15 @@ def build_core(model_names, device="cuda:0", dtype="bf16",
             io_dt = {"bf16": "BF16", "fp16": "FP16", "fp32": "FP32"}[dtype]
             fused = (densenet_fused or os.environ.get(
                 "CLIENT_AMD_DENSENET_FUSED") == "1")
+            module = densenet121(fused=fused)
+            if fused:
+                if stem_on:
+                    module.stem.enabled = True
+                module.fused_stem = stem_on
             core.add_model(
                 TorchModel(
                     "densenet121",
-                    densenet121(fused=fused),
+                    module,
                     inputs=[("INPUT0", io_dt, [-1, 3, 224, 224])],
                     outputs=[("OUTPUT0", io_dt, [-1, 1000])],
                     device=device,
@@ -252,6 +266,12 @@ def build_parser():
                              "kernels, each block on one buffer with no "
                              "concat (CLIENT_AMD_DENSENET_FUSED=1 does the "
                              "same)")
+    parser.add_argument("--fused-stem", action="store_true",
+                        help="run the stem of resnet50 and densenet121 (7x7 "
+                             "conv, bias, ReLU, max-pool) as one fused MFMA "
+                             "kernel (CLIENT_AMD_STEM_CONV=1 does the same); "
+                             "for densenet121 it has effect only together "
+                             "with --densenet-fused")
     parser.add_argument("--model-warmup", action="store_true",
                         help="pre-capture hipGraphs / prime MIOpen for the "
                              "serving batch sizes before READY is printed")
@@ -279,6 +299,7 @@ def main(argv=None):
         fp8_weight_gemm=args.fp8_weight_gemm,
         mxfp4_weight_gemm=args.mxfp4_weight_gemm,
         densenet_fused=args.densenet_fused,
+        fused_stem=args.fused_stem,
     )
     if args.dynamic_batching:
         for model in core.models.values():

@@ -610,7 +610,7 @@ class TorchModel(Model):
         for entry in cfg["input"]:
             if entry["name"] in self.optional_inputs:
                 entry["optional"] = True
-        for flag in ("fused_attention", "fused_dense_layers"):
+        for flag in ("fused_attention", "fused_dense_layers", "fused_stem"):
             if getattr(self.module, flag, False):
                 cfg.setdefault("parameters", {})[flag] = {
                     "string_value": "true"}
